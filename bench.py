@@ -15,6 +15,9 @@ the ONE exchange step of the multi-sequence configuration -- an RCCL
 per-window result records, device buffers, no host copy -- runs inside every timed step when N > 1.
   --scaling weak   (default) --windows per GPU (1024: BASELINE config 4's batch on every GPU)
   --scaling strong --windows in total, block-partitioned over the ranks (config 4 as written: 1024 / 8 = 128 per GPU)
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the last step computed for its windows (states, landmark
+                      depths, prior factors, solve summaries, marginalisation results) as DIR/<name>.npy, float64; the
+                      synthetic inputs are seeded by window id, so two builds can be compared output for output
 """
 import argparse
 import ctypes as C
@@ -144,6 +147,53 @@ def bs_flops(N):
     return fl
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _flat(obj):
+    """every number of a ctypes struct / array, in field order (padding skipped), as float64"""
+    import numpy as np
+    if isinstance(obj, C.Structure):
+        return np.concatenate([_flat(getattr(obj, f[0])) for f in obj._fields_ if not f[0].startswith("_pad")] or [np.zeros(0)])
+    if isinstance(obj, C.Array):
+        return np.concatenate([_flat(x) for x in obj] or [np.zeros(0)])
+    return np.array([float(obj)])
+
+
+def dump_outputs(out_dir, be, windows, ids):
+    """what a caller of the timed path receives from the resident batch after its last step: the windows' states, landmark
+    depths and updated prior factors (isv_batch_download), the solve summaries and the marginalisation results, one
+    DIR/<name>.npy (float64) each, row b = window ids[b].  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of windows."""
+    import numpy as np
+    ws = [w.clone() for w in windows]
+    sums, margs = be.download(ws)
+    Lmax = max(max(w.L for w in ws), 1)
+
+    def pad(a):
+        out = np.zeros(Lmax); out[: len(a)] = a
+        return out
+    arrays = {
+        "window_id": np.array(ids, dtype=np.float64), "n_landmarks": np.array([w.L for w in ws], dtype=np.float64),
+        "Ps": np.stack([w.Ps for w in ws]), "Rs": np.stack([w.Rs for w in ws]), "Vs": np.stack([w.Vs for w in ws]),
+        "Bas": np.stack([w.Bas for w in ws]), "Bgs": np.stack([w.Bgs for w in ws]),
+        "tic": np.stack([w.tic for w in ws]), "ric": np.stack([w.ric for w in ws]),
+        "para_Pose": np.stack([w.para_Pose for w in ws]), "para_SpeedBias": np.stack([w.para_SpeedBias for w in ws]),
+        "para_Ex_Pose": np.stack([w.para_Ex_Pose for w in ws]),
+        "para_Feature": np.stack([pad(w.para_Feature[: w.L]) for w in ws]), "lm_depth": np.stack([pad(w.lm_depth[: w.L]) for w in ws]),
+        "lm_solve_flag": np.stack([pad(w.lm_solve_flag[: w.L].astype(np.float64)) for w in ws]),
+        "pose_prior": np.stack([_flat(w.pose_prior) for w in ws]), "vb_prior": np.stack([_flat(w.vb_prior) for w in ws]),
+        "relpose": np.stack([_flat(w.relpose) for w in ws]), "rollpitch": np.stack([_flat(w.rollpitch) for w in ws]),
+        "summary": np.stack([_flat(x) for x in sums]), "marg": np.stack([_flat(x) for x in margs]),
+    }
+    total = sum(a.astype(np.float64).nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(ws), DUMP_LIMIT_BYTES * len(ws) // total, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,7 +206,10 @@ def main():
     ap.add_argument("--landmarks", type=int, default=300)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-legs", action="store_true", help="skip the untimed secondary legs (host-buffer rates, single window, config 2, N = 18, B = 128); used for the rocprofv3 passes so that their kernel statistics hold the benchmark's own launches only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     # ---- N > 1 without a launcher: start the ranks as a CHILD job.  This process has not imported torch or touched the
     # GPU and never will (a process that initialised the GPU must not exec / spawn rank processes on this pool).
@@ -173,9 +226,6 @@ def main():
         # equal shards only: all_gather_into_tensor needs the same record count on every rank
         sys.exit(f"bench.py: --scaling strong needs --windows ({args.windows}) divisible by the number of ranks ({world})")
 
-    # more than two handles' worth of HIP streams in one process (the untimed two-handle leg below): the runtime maps
-    # streams onto 4 hardware queues by default; must be set before the runtime initialises.  One handle is unaffected.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import numpy as np
     import torch
     # ISV_BENCH_REHEARSAL=1: rehearse the multi-rank path on ONE GPU (every rank on cuda:0, gloo instead of RCCL, which
@@ -185,7 +235,8 @@ def main():
     torch.cuda.set_device(dev)
     isvins_loader.load()
     from isvins_amd import backend, sharding, synth
-    backend.build()
+    # the library __graft_entry__.build() made (missing: an error); never rebuilt here, the tree may be read-only to this user
+    backend.load_library()
 
     W = args.windows if args.scaling == "weak" else None
     ids = list(sharding.shard_window_ids(rank, world, args.windows, None if args.scaling == "weak" else args.windows))
@@ -247,6 +298,8 @@ def main():
     dt = time.perf_counter() - t0
     if world > 1:
         dt = sharding.max_over_ranks(dt, dist, device="cpu" if rehearsal else f"cuda:{dev}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, be, windows, ids)
     # what the collective really connected: every rank's (rank, device index), gathered over the same process group
     ranks_seen = None
     if world > 1:

@@ -36,6 +36,8 @@ class BackendError(RuntimeError):
 def build(force=False):
     """compile every HIP source for gfx950 into csrc/libisvins_hip.so (hipcc cross-compiles)"""
     import fcntl
+    if not force and subprocess.call(["make", "-s", "-q", "-C", CSRC]) == 0:
+        return LIB_PATH                                              # up to date: nothing to write (the tree may be read-only)
     with open(os.path.join(CSRC, ".build.lock"), "w") as lock:      # ranks of one node may call this at the same time
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:

@@ -4,12 +4,15 @@ all-gather bench.py issues over RCCL (sharding.gather_records), and agree on the
 are disjoint and cover the batch, that every rank ends up with every window's record, and that a window's result does
 not depend on the rank count (windows are independent: no collective inside the solve)."""
 import ctypes as C
+import datetime
 import os
 import sys
+import threading
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+import torch
+import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_LM = 30
@@ -32,45 +35,63 @@ def _solve(lib, cfg, ids):
     return np.stack(recs)
 
 
-def _worker(rank, world, per_rank, port, q):
-    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import isvins_loader; isvins_loader.load()
-    import torch
-    import torch.distributed as dist
-    from isvins_amd import abi, sharding
-    import oracle_lib
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    lib = oracle_lib.load()
-    cfg = abi.make_config(11, 5)
-    out = {}
-    for mode, total in (("weak", None), ("strong", world * per_rank)):
-        ids = list(sharding.shard_window_ids(rank, world, per_rank, total))
-        recs = torch.from_numpy(_solve(lib, cfg, ids))
-        gathered = torch.empty((world * len(ids), recs.shape[1]), dtype=torch.float64)
-        sharding.gather_records(recs, gathered, dist)
-        out[mode] = (ids, gathered.numpy().copy())
-    dt = sharding.max_over_ranks(0.5 + rank, dist)      # pretend rank r took 0.5 + r seconds
-    q.put((rank, dt, out))
-    dist.barrier()
-    dist.destroy_process_group()
+class _RankGroup:
+    """one rank's gloo process group behind the torch.distributed calls sharding.py makes.  The ranks are threads of this
+    process, each with its own ProcessGroupGloo over a shared store: rank PROCESSES each import torch, and on a GPU
+    machine each of them may open the GPU, so that a CPU test would hold it open from nine processes at once"""
+    ReduceOp = dist.ReduceOp
+
+    def __init__(self, pg):
+        self.pg = pg
+
+    def is_initialized(self):
+        return True
+
+    def get_world_size(self):
+        return self.pg.size()
+
+    def all_gather_into_tensor(self, out, t):
+        self.pg._allgather_base(out, t).wait()
+
+    def all_gather(self, outs, t):
+        self.pg.allgather([outs], [t]).wait()
+
+    def all_reduce(self, t, op):
+        o = dist.AllreduceOptions(); o.reduceOp = op
+        self.pg.allreduce([t], o).wait()
+
+
+def _worker(rank, world, per_rank, store, got, errors):
+    try:
+        from isvins_amd import abi, sharding
+        import oracle_lib
+        group = _RankGroup(dist.ProcessGroupGloo(store, rank, world, datetime.timedelta(seconds=300)))
+        lib = oracle_lib.load()
+        cfg = abi.make_config(11, 5)
+        out = {}
+        for mode, total in (("weak", None), ("strong", world * per_rank)):
+            ids = list(sharding.shard_window_ids(rank, world, per_rank, total))
+            recs = torch.from_numpy(_solve(lib, cfg, ids))
+            gathered = torch.empty((world * len(ids), recs.shape[1]), dtype=torch.float64)
+            sharding.gather_records(recs, gathered, group)
+            out[mode] = (ids, gathered.numpy().copy())
+        dt = sharding.max_over_ranks(0.5 + rank, group)      # pretend rank r took 0.5 + r seconds
+        got[rank] = (dt, out)
+    except BaseException as ex:                             # (reported by _run_world: a thread's exception does not fail the test)
+        errors.append((rank, repr(ex)))
 
 
 def _run_world(world, per_rank):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29500 + (os.getpid() % 1000) + world
-    procs = [ctx.Process(target=_worker, args=(r, world, per_rank, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict()
-    for _ in range(world):
-        rank, dt, out = q.get(timeout=300)
-        got[rank] = (dt, out)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    store = dist.HashStore()
+    got, errors = {}, []
+    threads = [threading.Thread(target=_worker, args=(r, world, per_rank, store, got, errors)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=600)
+        assert not t.is_alive()
+    assert not errors and sorted(got) == list(range(world)), errors
     import oracle_lib
     from isvins_amd import abi
     ref = _solve(oracle_lib.load(), abi.make_config(11, 5), range(world * per_rank))      # the same windows in ONE process

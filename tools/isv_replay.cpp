@@ -265,10 +265,6 @@ void run_group(const Stream &st, int first_seq, int n_seq, const std::string &ou
 }  // namespace
 
 int main(int argc, char **argv) {
-    // every estimator owns two HIP streams; the runtime multiplexes a process's streams onto 4 hardware queues by default,
-    // which serialises the groups' fork / join patterns against each other (256 sequences in 4 groups: 15.7 k frames/s
-    // with 4 queues, 27.8 k with 16).  Ask for more before the runtime initialises, unless the caller has chosen.
-    setenv("GPU_MAX_HW_QUEUES", "16", 0);
     if (argc < 2) { fprintf(stderr, "usage: isv_replay STREAM | --euroc MAV0_DIR --tracks CSV --config TXT  [--sequences S] [--groups K] [--out DIR] [--write W] [--no-resident]\n"); return 2; }
     int S = 1, K = 0, W = 1;                        // K = 0: choose the groups from the sequence count
     bool resident = true;                           // windows kept on the device between frames (--no-resident: re-upload every frame)
