@@ -58,6 +58,11 @@ struct isv_backend {
     int device = 0;               // the HIP device the handle was created on; every entry point re-selects it
     double *init_scratch = nullptr, *init_kld = nullptr;   // initFactorGraph scratch, allocated on first use and kept
     size_t init_cap = 0;
+    // isv_internal_visual_imu_align_batch (isv_initial.hip): its device block (grow-only), kernel events, last call's times
+    void *align_d = nullptr; size_t align_cap = 0;
+    hipEvent_t align_ev[2] = {};
+    double align_call_ms = 0, align_kernel_ms = 0;
+    void (*free_align)(isv_backend *) = nullptr;
     double last_ms[8] = {};
     int64_t last_counts[8] = {};
     hipGraphExec_t graph_exec = nullptr;    // ISV_GRAPH=1 (measurement hook): the captured launch chain of isv_batch_optimize
