@@ -63,6 +63,11 @@ struct isv_backend {
     hipEvent_t align_ev[2] = {};
     double align_call_ms = 0, align_kernel_ms = 0;
     void (*free_align)(isv_backend *) = nullptr;
+    // isv_internal_sfm_batch (isv_sfm.hip): the same pattern
+    void *sfm_d = nullptr; size_t sfm_cap = 0;
+    hipEvent_t sfm_ev[2] = {};
+    double sfm_call_ms = 0, sfm_kernel_ms = 0;
+    void (*free_sfm)(isv_backend *) = nullptr;
     double last_ms[8] = {};
     int64_t last_counts[8] = {};
     hipGraphExec_t graph_exec = nullptr;    // ISV_GRAPH=1 (measurement hook): the captured launch chain of isv_batch_optimize

@@ -1,7 +1,9 @@
 /*
  * isv_initial.h -- INTERNAL entry point of the visual-inertial alignment stage of the estimator's initialisation, batched over
  * sequences on the MI355X.  Not part of the public ABI (include/): it is the building block of the window manager's
- * self-initialisation (initialStructure: relative-pose RANSAC, SfM, all-frame PnP, then this stage), which is not built yet.
+ * self-initialisation (initialStructure: relative-pose RANSAC, SfM, all-frame PnP, then this stage).  The SfM and the all-frame
+ * PnP are isv_sfm.h, whose results fill this stage's R / T / is_key_frame; the relative-pose RANSAC and the window manager's
+ * wiring are not built yet.
  * The library exports it as isv_internal_visual_imu_align_batch for its own tests and scripts/init_bench.py only; its
  * layout may change with that work.  Stages:
  *   solveGyroscopeBias                    src/initial/initial_aligment.cpp:3-37

@@ -185,3 +185,265 @@ def ate_4dof(res, truth, n):
     eg = np.linalg.norm(np.array(res.g) - truth["G"])
     es = abs(res.s - truth["scale"]) / truth["scale"]
     return ep, er, ev, eg, es
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The SfM stage (is-vins_amd/csrc/isv_sfm.h): IMU excitation, GlobalSFM::construct with its BA, the all-frame PnP.
+
+ISV_SFM_MAX_TRACKS = 1024
+ISV_SFM_MAX_OBS = 4096
+SFM_STATUS = {0: "ok", 1: "excitation", 2: "sfm_pnp_points", 3: "ba_not_converged", 4: "all_pnp_points", 5: "capacity", 6: "input"}
+_W, _F = ISV_ALIGN_MAX_WINDOW, ISV_ALIGN_MAX_FRAMES
+
+
+class isv_sfm_track_t(C.Structure):
+    _fields_ = [("id", C.c_int32), ("start_frame", C.c_int32), ("n_obs", C.c_int32), ("obs_off", C.c_int32)]
+
+
+class isv_sfm_problem_t(C.Structure):
+    _fields_ = [("n_window", C.c_int32), ("n_frames", C.c_int32), ("l", C.c_int32), ("n_tracks", C.c_int32), ("n_obs", C.c_int32),
+                ("n_pts", C.c_int32), ("relative_R", C.c_double * 9), ("relative_T", C.c_double * 3), ("RIC", C.c_double * 9),
+                ("tracks", C.POINTER(isv_sfm_track_t)), ("obs", C.POINTER(C.c_double)), ("pt_off", C.POINTER(C.c_int32)),
+                ("pt_id", C.POINTER(C.c_int32)), ("pt_uv", C.POINTER(C.c_double)), ("delta_v", C.POINTER(C.c_double)),
+                ("sum_dt", C.POINTER(C.c_double)), ("window_frame", C.c_int32 * _W),
+                ("position", C.POINTER(C.c_double)), ("state", C.POINTER(C.c_int32))]
+
+
+class isv_sfm_result_t(C.Structure):
+    _fields_ = [("status", C.c_int32), ("fail_frame", C.c_int32), ("ba_iterations", C.c_int32), ("ba_termination", C.c_int32),
+                ("ba_residuals", C.c_int32), ("ba_successful", C.c_int32), ("n_triangulated", C.c_int32), ("n_ba_cols", C.c_int32),
+                ("excitation_var", C.c_double), ("ba_initial_cost", C.c_double), ("ba_final_cost", C.c_double),
+                ("Q", (C.c_double * 4) * _W), ("T", (C.c_double * 3) * _W),
+                ("sfm_pnp_iterations", C.c_int32 * _W), ("sfm_pnp_points", C.c_int32 * _W),
+                ("R", (C.c_double * 9) * _F), ("Tf", (C.c_double * 3) * _F), ("is_key_frame", C.c_int32 * _F),
+                ("pnp_iterations", C.c_int32 * _F), ("pnp_points", C.c_int32 * _F)]
+
+    def arr(self, name):
+        return np.ctypeslib.as_array(getattr(self, name)).copy()
+
+
+class SfmProblem:
+    """one isv_sfm_problem_t, the arrays it points into and its per-track outputs (kept alive with it)"""
+
+    def __init__(self, n_window, l, relative_R, relative_T, RIC, tracks, obs, frame_pts, delta_v, sum_dt, window_frame):
+        """tracks: [(id, start_frame, n_obs)] in IDsfeatures order, obs: [sum n_obs][2] in track order; frame_pts: per
+        all_image_frame entry a list of (feature_id, u, v) ascending by id; delta_v [n_frames][3], sum_dt [n_frames]"""
+        n_frames = len(frame_pts)
+        self.tracks = (isv_sfm_track_t * max(len(tracks), 1))()
+        off = 0
+        for j, (tid, s, n) in enumerate(tracks):
+            self.tracks[j].id, self.tracks[j].start_frame, self.tracks[j].n_obs, self.tracks[j].obs_off = int(tid), int(s), int(n), off
+            off += int(n)
+        self.obs = np.ascontiguousarray(np.asarray(obs, dtype=np.float64).reshape(-1, 2))
+        self.pt_off = np.zeros(n_frames + 1, dtype=np.int32)
+        ids, uvs = [], []
+        for f, pts in enumerate(frame_pts):
+            for (i, u, v) in pts:
+                ids.append(int(i)); uvs.append((u, v))
+            self.pt_off[f + 1] = len(ids)
+        self.pt_id = np.array(ids if ids else [0], dtype=np.int32)
+        self.pt_uv = np.ascontiguousarray(np.array(uvs if uvs else [(0.0, 0.0)], dtype=np.float64).reshape(-1, 2))
+        self.delta_v = np.ascontiguousarray(np.asarray(delta_v, dtype=np.float64).reshape(-1, 3))
+        self.sum_dt = np.ascontiguousarray(np.asarray(sum_dt, dtype=np.float64))
+        self.position = np.zeros((max(len(tracks), 1), 3))
+        self.state = np.zeros(max(len(tracks), 1), dtype=np.int32)
+        c = self.c = isv_sfm_problem_t()
+        c.n_window, c.n_frames, c.l, c.n_tracks, c.n_obs, c.n_pts = n_window, n_frames, l, len(tracks), off, len(ids)
+        c.relative_R[:] = np.asarray(relative_R, dtype=np.float64).ravel().tolist()
+        c.relative_T[:] = np.asarray(relative_T, dtype=np.float64).ravel().tolist()
+        c.RIC[:] = np.asarray(RIC, dtype=np.float64).ravel().tolist()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        c.tracks = C.cast(self.tracks, C.POINTER(isv_sfm_track_t))
+        c.obs = self.obs.ctypes.data_as(dp)
+        c.pt_off, c.pt_id, c.pt_uv = self.pt_off.ctypes.data_as(ip), self.pt_id.ctypes.data_as(ip), self.pt_uv.ctypes.data_as(dp)
+        c.delta_v, c.sum_dt = self.delta_v.ctypes.data_as(dp), self.sum_dt.ctypes.data_as(dp)
+        for i, w in enumerate(window_frame):
+            c.window_frame[i] = int(w)
+        c.position, c.state = self.position.ctypes.data_as(dp), self.state.ctypes.data_as(ip)
+        self.truth = {}
+
+
+def _bind_sfm(lib):
+    if getattr(lib, "_sfm_bound", False):
+        return
+    lib.isv_internal_sfm_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(isv_sfm_problem_t)), C.POINTER(isv_sfm_result_t)]
+    lib.isv_internal_sfm_batch.restype = C.c_int
+    lib.isv_internal_sfm_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.isv_internal_sfm_last_ms.restype = C.c_int
+    lib._sfm_bound = True
+
+
+def sfm_batch(be, problems):
+    """isv_internal_sfm_batch on the backend handle `be`; returns the results (each problem's position / state arrays are
+    filled in place)"""
+    lib = be.lib
+    _bind_sfm(lib)
+    n = len(problems)
+    ptrs = (C.POINTER(isv_sfm_problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
+    res = (isv_sfm_result_t * max(n, 1))()
+    rc = lib.isv_internal_sfm_batch(be.h, n, ptrs, res)
+    if rc != 0:
+        raise backend.BackendError(f"isv_internal_sfm_batch: {backend.STATUS.get(rc, rc)}: {lib.isv_backend_last_error(be.h)}")
+    return [res[i] for i in range(n)]
+
+
+def sfm_last_ms(be):
+    """(whole call, kernel) milliseconds of the last sfm_batch on this handle"""
+    _bind_sfm(be.lib)
+    out = (C.c_double * 2)()
+    be.lib.isv_internal_sfm_last_ms(be.h, out)
+    return out[0], out[1]
+
+
+def copy_sfm_to_align(res, align_problem):
+    """ImageFrame::R / T / is_key_frame of every all_image_frame entry, as the SfM result has them, into an alignment problem"""
+    for f in range(align_problem.c.n_frames):
+        fr = align_problem.frames[f]
+        fr.R[:] = list(res.R[f]); fr.T[:] = list(res.Tf[f]); fr.is_key_frame = res.is_key_frame[f]
+
+
+def initial_structure_batch(be, sfm_problems, align_problems):
+    """initialStructure after relativePose: the SfM stage on every problem, then the alignment on the problems whose SfM
+    succeeded (their R / T / is_key_frame copied in).  Returns (sfm results, alignment results with None where the SfM
+    refused)"""
+    sr = sfm_batch(be, sfm_problems)
+    ok = [i for i, r in enumerate(sr) if r.status == 0]
+    for i in ok:
+        copy_sfm_to_align(sr[i], align_problems[i])
+    ar = align_batch(be, [align_problems[i] for i in ok]) if ok else []
+    out = [None] * len(sfm_problems)
+    for i, r in zip(ok, ar):
+        out[i] = r
+    return sr, out
+
+
+def _rotvec(w):
+    th = np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th == 0:
+        return np.eye(3)
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
+
+
+def make_scene(seed=0, n_window=11, extra=0, l=None, per_frame=150, pixel_noise=0.0, rel_rot_err=0.0, rel_dir_err=0.0,
+               cam_dt=0.1, imu_per_frame=10, acc_noise=0.0, gyr_noise=0.0, depth=(6.0, 16.0), max_obs=ISV_SFM_MAX_OBS, behind=0, **kw):
+    """a seeded synthetic initialisation scene: (SfmProblem, alignment Problem).  The trajectory and IMU are make_problem's
+    (same seed), with `extra` non-keyframes spread between the window frames of all_image_frame (S4).  Landmarks lie
+    `depth` metres in front of the camera of their first frame and are tracked through RIC / TIC by a pinhole camera for
+    2..n_window consecutive window frames while in view (about `per_frame` observations per frame, at most max_obs in all).
+    relative_R / T between l (default n_window // 2) and the last window frame come from ground truth with |T| = 1, turned by
+    rel_rot_err [rad] and rel_dir_err [rad] when given.  pixel_noise: white noise on the normalised image points.  behind:
+    that many extra tracks of a point BEHIND the cameras of window frames 0 and 1 (only step 5 triangulates them, S5).
+    truth: the SfM frame's Q / T (camera i to camera l, unit baseline), the landmarks in it, every frame's R / T as the
+    all-frame PnP should give them; the alignment problem's truth scale is the baseline in metres."""
+    n_frames = n_window + extra
+    window = sorted(set(np.linspace(0, n_frames - 1, n_window).round().astype(int).tolist()))
+    assert len(window) == n_window
+    ap = make_problem(seed=seed, n_frames=n_frames, window_frame=window, cam_dt=cam_dt, imu_per_frame=imu_per_frame, sfm_scale=1.0,
+                      acc_noise=acc_noise, gyr_noise=gyr_noise, **kw)
+    ric = synth.RIC
+    rng = synth.SplitMix64(0x5F3D00000000 + seed)
+    l = n_window // 2 if l is None else l
+    Rc = [np.array(ap.frames[f].R).reshape(3, 3) @ ric for f in range(n_frames)]   # camera to c0
+    Cc = [np.array(ap.frames[f].T) for f in range(n_frames)]                       # camera centres in c0 (metres)
+    wl, wlast = window[l], window[-1]
+    base = np.linalg.norm(Cc[wlast] - Cc[wl]) or 1.0   # (a hovering body: no baseline)
+    to_l = lambda X: Rc[wl].T @ (X - Cc[wl]) / base                                  # noqa: E731
+    # landmarks
+    tracks, obs, lms, truth_pts = [], [], [], []
+    mean_len = (2 + n_window) / 2.5
+    n_lm = int(round(per_frame * n_window / mean_len))
+    u = rng.uniform(6 * n_lm * 4).reshape(-1, 6)
+    nz = rng.normal(2 * n_lm * n_window * 4 + 2 * n_frames * n_lm).tolist()
+    ni = iter(nz)
+    next_id = 7
+    k = 0
+    while len(tracks) < n_lm and k < len(u):
+        s = int(u[k, 0] * (n_window - 1))
+        L = max(2, int(np.sqrt(u[k, 1]) * (n_window + 1)))
+        L = min(L, n_window - s)
+        d = depth[0] + (depth[1] - depth[0]) * u[k, 2]
+        xy = (u[k, 3:5] - 0.5) * 1.2
+        X = Rc[window[s]] @ (np.array([xy[0], xy[1], 1.0]) * d) + Cc[window[s]]
+        k += 1
+        uv = []
+        for i in range(s, s + L):
+            xc = Rc[window[i]].T @ (X - Cc[window[i]])
+            if xc[2] < 0.2 or abs(xc[0] / xc[2]) > 1.2 or abs(xc[1] / xc[2]) > 1.2:
+                break
+            uv.append(xc[:2] / xc[2])
+        if len(uv) < 2 or len(obs) + len(uv) > max_obs:
+            continue
+        uv = [p + pixel_noise * np.array([next(ni), next(ni)]) for p in uv]
+        tracks.append((next_id, s, len(uv)))
+        obs.extend(uv)
+        lms.append(X)
+        truth_pts.append(to_l(X))
+        next_id += 1 + int(u[k - 1, 5] * 3)
+    for b in range(behind):
+        X = Rc[window[0]] @ (np.array([0.1 * b - 0.2, 0.15, -1.0]) * 5.0) + Cc[window[0]]
+        uv = [(Rc[window[i]].T @ (X - Cc[window[i]]))[:2] / (Rc[window[i]].T @ (X - Cc[window[i]]))[2] for i in (0, 1)]
+        tracks.append((next_id, 0, 2)); obs.extend(uv); lms.append(X); truth_pts.append(to_l(X))
+        next_id += 1
+    # all_image_frame's points: the window frames' own observations; a non-keyframe sees the tracks alive at both neighbours
+    frame_pts = [[] for _ in range(n_frames)]
+    off = 0
+    for (tid, s, n), X in zip(tracks, lms):
+        for i in range(n):
+            frame_pts[window[s + i]].append((tid, obs[off + i][0], obs[off + i][1]))
+        for f in range(n_frames):
+            if f in window:
+                continue
+            i1 = int(np.searchsorted(window, f))
+            if s <= i1 - 1 and i1 < s + n:
+                xc = Rc[f].T @ (X - Cc[f])
+                if xc[2] > 0.2:
+                    p = xc[:2] / xc[2] + pixel_noise * np.array([next(ni), next(ni)])
+                    frame_pts[f].append((tid, p[0], p[1]))
+        off += n
+    for f in range(n_frames):
+        frame_pts[f].sort(key=lambda e: e[0])
+    # pre-integration delta_v / sum_dt of every frame (stage 0)
+    dv, sdt = np.zeros((n_frames, 3)), np.zeros(n_frames)
+    for f in range(1, n_frames):
+        fr = ap.frames[f]
+        rows = ap.imu[fr.imu_begin:fr.imu_begin + fr.imu_count]
+        acc = np.vstack([np.array(fr.linearized_acc), rows[:, 1:4]])
+        gyr = np.vstack([np.array(fr.linearized_gyr), rows[:, 4:7]])
+        pre = synth.preintegrate(rows[0, 0], acc[None], gyr[None], np.zeros((1, 3)), np.zeros((1, 3)))
+        dv[f], sdt[f] = pre["delta_v"][0], pre["sum_dt"]
+    relR = Rc[wl].T @ Rc[wlast]
+    relT = to_l(Cc[wlast])
+    if rel_rot_err:
+        a = np.array([0.3, -0.5, 0.8]); relR = _rotvec(rel_rot_err * a / np.linalg.norm(a)) @ relR
+    if rel_dir_err:
+        a = np.cross(relT, [0.2, 0.9, -0.4]); relT = _rotvec(rel_dir_err * a / np.linalg.norm(a)) @ relT
+    sp = SfmProblem(n_window, l, relR, relT, ric, tracks, obs, frame_pts, dv, sdt, window)
+    sp.truth = dict(Q=np.array([Rc[wl].T @ Rc[w] for w in window]), T=np.array([to_l(Cc[w]) for w in window]),
+                    points=np.array(truth_pts).reshape(-1, 3), R=np.array([Rc[wl].T @ Rc[f] @ ric.T for f in range(n_frames)]),
+                    Tf=np.array([to_l(Cc[f]) for f in range(n_frames)]), base=base)
+    ap.truth["scale"] = base
+    return sp, ap
+
+
+def q_to_R(q):
+    """x y z w -> rotation matrix (normalised)"""
+    x, y, z, w = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def sfm_errors(res, sp):
+    """errors of an OK SfM result against the scene's truth (the SfM frame is fixed by camera l and the unit baseline, so no
+    similarity is left to fit): (max rotation error of Q [Frobenius], max |T - T_gt|, max point error, max all-frame R error,
+    max all-frame T error)"""
+    tr = sp.truth
+    nw, nf = sp.c.n_window, sp.c.n_frames
+    eq = max(np.linalg.norm(q_to_R(res.Q[i]) - tr["Q"][i]) for i in range(nw))
+    et = np.abs(np.array([list(res.T[i]) for i in range(nw)]) - tr["T"]).max()
+    st = sp.state[:sp.c.n_tracks].astype(bool)
+    ep = np.abs(sp.position[:sp.c.n_tracks][st] - tr["points"][st]).max() if st.any() else 0.0
+    eR = max(np.linalg.norm(np.array(res.R[f]).reshape(3, 3) - tr["R"][f]) for f in range(nf))
+    eT = np.abs(np.array([list(res.Tf[f]) for f in range(nf)]) - tr["Tf"]).max()
+    return eq, et, ep, eR, eT
