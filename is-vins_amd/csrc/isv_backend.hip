@@ -31,6 +31,7 @@ extern "C" void isv_backend_destroy(isv_backend_t *h) {
     if (h->init_kld) (void)hipFree(h->init_kld);
     if (h->free_align) h->free_align(h);
     if (h->free_sfm) h->free_sfm(h);
+    if (h->free_relpose) h->free_relpose(h);
     for (void *p : h->allocs) (void)hipFree(p);
     for (void *p : h->hallocs) (void)hipHostFree(p);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);

@@ -68,6 +68,11 @@ struct isv_backend {
     hipEvent_t sfm_ev[2] = {};
     double sfm_call_ms = 0, sfm_kernel_ms = 0;
     void (*free_sfm)(isv_backend *) = nullptr;
+    // isv_internal_relpose_batch (isv_relpose.hip): the same pattern
+    void *relpose_d = nullptr; size_t relpose_cap = 0;
+    hipEvent_t relpose_ev[2] = {};
+    double relpose_call_ms = 0, relpose_kernel_ms = 0;
+    void (*free_relpose)(isv_backend *) = nullptr;
     double last_ms[8] = {};
     int64_t last_counts[8] = {};
     hipGraphExec_t graph_exec = nullptr;    // ISV_GRAPH=1 (measurement hook): the captured launch chain of isv_batch_optimize

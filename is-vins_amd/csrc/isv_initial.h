@@ -2,8 +2,8 @@
  * isv_initial.h -- INTERNAL entry point of the visual-inertial alignment stage of the estimator's initialisation, batched over
  * sequences on the MI355X.  Not part of the public ABI (include/): it is the building block of the window manager's
  * self-initialisation (initialStructure: relative-pose RANSAC, SfM, all-frame PnP, then this stage).  The SfM and the all-frame
- * PnP are isv_sfm.h, whose results fill this stage's R / T / is_key_frame; the relative-pose RANSAC and the window manager's
- * wiring are not built yet.
+ * PnP are isv_sfm.h, whose results fill this stage's R / T / is_key_frame; the relative-pose RANSAC before it is isv_relpose.h.
+ * The window manager's wiring is not built yet.
  * The library exports it as isv_internal_visual_imu_align_batch for its own tests and scripts/init_bench.py only; its
  * layout may change with that work.  Stages:
  *   solveGyroscopeBias                    src/initial/initial_aligment.cpp:3-37
@@ -15,7 +15,8 @@
  * One problem = one sequence's all_image_frame after GlobalSFM::construct and the all-frame PnP of
  * Estimator::initialStructure (src/estimator.cpp:239-349): per frame the SfM rotation R (= R_pnp * RIC^T) and camera centre T
  * (up to scale) in the frame of the SfM's reference camera, the frame's pre-integration since the previous image, and its raw
- * IMU samples.  The relative-pose RANSAC, the SfM and the PnP that produce R / T are NOT part of this ABI.
+ * IMU samples.  The relative-pose RANSAC, the SfM and the PnP that produce R / T are separate entry points (isv_relpose.h,
+ * isv_sfm.h).
  *
  * The caller's share of visualInitialAlign (host or other kernels of this library):
  *   - the depth reset + f_manager.triangulate with tic = 0 and the `estimated_depth *= s` of good features (:378-411)

@@ -1,7 +1,7 @@
 /*
  * isv_sfm.h -- INTERNAL entry point of the structure-from-motion stage of the estimator's initialisation, batched over
- * sequences on the MI355X.  Not part of the public ABI (include/).  It sits between the relative-pose RANSAC (not built:
- * `l` and relative_R / relative_T are inputs) and the visual-inertial alignment of isv_initial.h, whose per-frame inputs
+ * sequences on the MI355X.  Not part of the public ABI (include/).  It sits between the relative-pose RANSAC of isv_relpose.h
+ * (which finds the `l` and relative_R / relative_T this stage takes) and the visual-inertial alignment of isv_initial.h, whose per-frame inputs
  * (isv_align_frame_t::R, T, is_key_frame) it produces.  The library exports it as isv_internal_sfm_batch for its own tests
  * and scripts/init_bench.py only; its layout may change with the window manager's wiring.  Stages, per problem:
  *   0 Estimator::checkIMUExcitation       src/estimator.cpp:213-238

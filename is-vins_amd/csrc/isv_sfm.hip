@@ -23,6 +23,7 @@
 #include <vector>
 #include "isv_backend_impl.h"
 #include "isv_sfm.h"
+#include "isv_init_common.h"
 
 namespace {
 
@@ -42,94 +43,8 @@ struct SfmHdr {                   // host-packed per-problem record
 };
 
 // the restatement's per-lane serial pieces (Eigen JacobiSVD / quaternion, OpenCV Rodrigues / projection / LM step, Ceres'
-// rotation, Plus and the 3 x 3 LLT inverse); the same text as tests/native/isv_sfm_oracle.c
-/* ---------------- Eigen 3.3 JacobiSVD, square n x n (n <= 6), no QR preconditioner ---------------- */
-/* A row-major, overwritten; w: singular values (sorted, descending); U (may be NULL), V: n x n row-major */
-static __device__ void svd_jacobi(int n, double *A, double *w, double *U, double *V) {
-    double scale = 0;
-    for (int k = 0; k < n * n; k++) scale = fabs(A[k]) > scale ? fabs(A[k]) : scale;
-    if (scale == 0.0) scale = 1.0;
-    for (int k = 0; k < n * n; k++) A[k] /= scale;
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) {
-            V[i * n + j] = i == j ? 1.0 : 0.0;
-            if (U) U[i * n + j] = i == j ? 1.0 : 0.0;
-        }
-    const double considerAsZero = DBL_MIN, precision = 2.0 * DBL_EPSILON;
-    double maxDiag = 0;
-    for (int i = 0; i < n; i++) maxDiag = fabs(A[i * n + i]) > maxDiag ? fabs(A[i * n + i]) : maxDiag;
-    int finished = 0;
-    for (int sweep = 0; !finished && sweep < 64; sweep++) {   /* (Eigen has no sweep cap; 64 is never reached on finite input) */
-        finished = 1;
-        for (int p = 1; p < n; p++)
-            for (int q = 0; q < p; q++) {
-                double thr = precision * maxDiag > considerAsZero ? precision * maxDiag : considerAsZero;
-                if (!(fabs(A[p * n + q]) > thr || fabs(A[q * n + p]) > thr)) continue;
-                finished = 0;
-                /* real_2x2_jacobi_svd */
-                double m00 = A[p * n + p], m01 = A[p * n + q], m10 = A[q * n + p], m11 = A[q * n + q];
-                double c1, s1;
-                double t = m00 + m11, d = m10 - m01;
-                if (fabs(d) < DBL_MIN) { s1 = 0.0; c1 = 1.0; }
-                else { double u = t / d, tmp = sqrt(1.0 + u * u); s1 = 1.0 / tmp; c1 = u / tmp; }
-                { double a0 = m00, a1 = m01, b0 = m10, b1 = m11;   /* m.applyOnTheLeft(0, 1, rot1) */
-                  m00 = c1 * a0 + s1 * b0; m01 = c1 * a1 + s1 * b1; m10 = -s1 * a0 + c1 * b0; m11 = -s1 * a1 + c1 * b1; }
-                double cr, sr;   /* j_right.makeJacobi(m, 0, 1) */
-                {
-                    double deno = 2.0 * fabs(m01);
-                    if (deno < DBL_MIN) { cr = 1.0; sr = 0.0; }
-                    else {
-                        double tau = (m00 - m11) / deno, ww = sqrt(tau * tau + 1.0), tt;
-                        tt = tau > 0.0 ? 1.0 / (tau + ww) : 1.0 / (tau - ww);
-                        double sign_t = tt > 0.0 ? 1.0 : -1.0, nn = 1.0 / sqrt(tt * tt + 1.0);
-                        sr = -sign_t * (m01 / fabs(m01)) * fabs(tt) * nn;
-                        cr = nn;
-                    }
-                }
-                /* j_left = rot1 * j_right.transpose() */
-                const double so = -sr;
-                const double cl = c1 * cr - s1 * so, sl = c1 * so + s1 * cr;
-                for (int k = 0; k < n; k++) {   /* A.applyOnTheLeft(p, q, j_left) */
-                    double x = A[p * n + k], y = A[q * n + k];
-                    A[p * n + k] = cl * x + sl * y; A[q * n + k] = -sl * x + cl * y;
-                }
-                if (U) for (int k = 0; k < n; k++) {   /* U.applyOnTheRight(p, q, j_left.transpose()) */
-                    double x = U[k * n + p], y = U[k * n + q];
-                    U[k * n + p] = cl * x + sl * y; U[k * n + q] = -sl * x + cl * y;
-                }
-                for (int k = 0; k < n; k++) {   /* A.applyOnTheRight(p, q, j_right) */
-                    double x = A[k * n + p], y = A[k * n + q];
-                    A[k * n + p] = cr * x + so * y; A[k * n + q] = -so * x + cr * y;
-                }
-                for (int k = 0; k < n; k++) {   /* V.applyOnTheRight(p, q, j_right) */
-                    double x = V[k * n + p], y = V[k * n + q];
-                    V[k * n + p] = cr * x + so * y; V[k * n + q] = -so * x + cr * y;
-                }
-                double ap = fabs(A[p * n + p]), aq = fabs(A[q * n + q]);
-                double mx = ap > aq ? ap : aq;
-                maxDiag = maxDiag > mx ? maxDiag : mx;
-            }
-    }
-    for (int i = 0; i < n; i++) {
-        double a = A[i * n + i];
-        w[i] = fabs(a);
-        if (U && a < 0.0) for (int k = 0; k < n; k++) U[k * n + i] = -U[k * n + i];
-    }
-    for (int i = 0; i < n; i++) w[i] *= scale;
-    for (int i = 0; i < n; i++) {   /* sort: tail(n - i).maxCoeff(&pos), first on ties */
-        int pos = i;
-        for (int k = i + 1; k < n; k++) if (w[k] > w[pos]) pos = k;
-        if (w[pos] == 0.0) break;
-        if (pos != i) {
-            double tw = w[i]; w[i] = w[pos]; w[pos] = tw;
-            for (int k = 0; k < n; k++) {
-                double tv = V[k * n + i]; V[k * n + i] = V[k * n + pos]; V[k * n + pos] = tv;
-                if (U) { double tu = U[k * n + i]; U[k * n + i] = U[k * n + pos]; U[k * n + pos] = tu; }
-            }
-        }
-    }
-}
-
+// rotation, Plus and the 3 x 3 LLT inverse); the same text as tests/native/isv_sfm_oracle.c (svd_jacobi and the excitation
+// check are in isv_init_common.h, shared with isv_relpose.hip)
 /* GlobalSFM::triangulatePoint: P0 / P1 are 3 x 4 row-major [R | t] */
 static __device__ void triangulate(const double *P0, const double *P1, const double *x0, const double *x1, double *out) {
     double A[16], w[4], V[16];
@@ -848,18 +763,7 @@ __global__ void __launch_bounds__(kLanes) k_sfm(const SfmHdr *__restrict__ hdrs,
 
     // ---- stage 0: checkIMUExcitation (lane 0) ----
     if (t == 0) {
-        const double *dv = dv_g + 3 * (size_t)H.frame_off, *sdt = sdt_g + H.frame_off;
-        double sum_g[3] = {0, 0, 0};   // S1: never initialised in the reference; zero here
-        for (int f = 1; f < nf; f++) for (int k = 0; k < 3; k++) sum_g[k] += dv[3 * f + k] / sdt[f];
-        double aver[3];
-        for (int k = 0; k < 3; k++) aver[k] = sum_g[k] * 1.0 / (double)(nf - 1);
-        double var = 0;
-        for (int f = 1; f < nf; f++) {
-            double d[3];
-            for (int k = 0; k < 3; k++) d[k] = dv[3 * f + k] / sdt[f] - aver[k];
-            var += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        }
-        var = sqrt(var / (double)(nf - 1));
+        const double var = isv_excitation_var(nf, dv_g + 3 * (size_t)H.frame_off, sdt_g + H.frame_off);   // S1 (isv_init_common.h)
         res->excitation_var = var;
         misc[M_FLAG] = var < 0.25 ? 1.0 : 0.0;
         // ---- stage 1 set-up: frames l and last ----
@@ -1060,11 +964,14 @@ size_t lds_bytes(int nt_max, int no_max, int nS) {
            sizeof(int16_t) * (size_t)((nt_max + 3) & ~3) + (size_t)nt_max;
 }
 
-// the host-side refusals: capacity, then the shape of the input (isv_sfm.h)
-int check_problem(const isv_sfm_problem_t *p) {
+}  // namespace
+
+// the host-side refusals: capacity, then the shape of the input (isv_sfm.h); the relative-pose stage (isv_relpose.hip) runs
+// the same checks with_l = false, as it does not read l
+int isv_sfm_check_problem(const isv_sfm_problem_t *p, bool with_l) {
     if (p->n_window > ISV_ALIGN_MAX_WINDOW || p->n_frames > ISV_ALIGN_MAX_FRAMES || p->n_tracks > ISV_SFM_MAX_TRACKS || p->n_obs > ISV_SFM_MAX_OBS)
         return ISV_SFM_REFUSED_CAPACITY;
-    if (p->n_window < 2 || p->n_frames < 2 || p->l < 0 || p->l >= p->n_window - 1 || p->n_tracks < 0 || p->n_obs < 0 || p->n_pts < 0)
+    if (p->n_window < 2 || p->n_frames < 2 || (with_l && (p->l < 0 || p->l >= p->n_window - 1)) || p->n_tracks < 0 || p->n_obs < 0 || p->n_pts < 0)
         return ISV_SFM_REFUSED_INPUT;
     if ((p->n_tracks && (!p->tracks || !p->obs)) || !p->pt_off || (p->n_pts && (!p->pt_id || !p->pt_uv)) || !p->delta_v || !p->sum_dt)
         return ISV_SFM_REFUSED_INPUT;
@@ -1087,6 +994,8 @@ int check_problem(const isv_sfm_problem_t *p) {
     }
     return ISV_SFM_OK;
 }
+
+namespace {
 
 std::mutex g_sfm_attr_mutex;
 
@@ -1128,7 +1037,7 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
         const isv_sfm_problem_t *p = problems[i];
         SfmHdr &H = hd[i];
         memset(&H, 0, sizeof(H));
-        H.status = check_problem(p);
+        H.status = isv_sfm_check_problem(p, true);
         if (H.status != ISV_SFM_OK) continue;
         H.nw = p->n_window; H.nf = p->n_frames; H.l = p->l; H.ntr = p->n_tracks; H.nobs = p->n_obs; H.npts = p->n_pts;
         H.trk_off = (int32_t)n_tr; H.obs_off = (int32_t)n_obs; H.pt_off_off = (int32_t)n_poff; H.pt_base = (int32_t)n_pts; H.frame_off = (int32_t)n_fr;

@@ -447,3 +447,113 @@ def sfm_errors(res, sp):
     eR = max(np.linalg.norm(np.array(res.R[f]).reshape(3, 3) - tr["R"][f]) for f in range(nf))
     eT = np.abs(np.array([list(res.Tf[f]) for f in range(nf)]) - tr["Tf"]).max()
     return eq, et, ep, eR, eT
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The relative-pose stage (is-vins_amd/csrc/isv_relpose.h): IMU excitation, then relativePose's candidates, each a
+# findFundamentalMat RANSAC and recoverPose.  It reads the SfM problem and ignores its l / relative_R / relative_T.
+
+RELPOSE_STATUS = {0: "ok", 1: "excitation", 2: "no_relative_pose", 3: "capacity", 4: "input"}
+
+
+class isv_relpose_result_t(C.Structure):
+    _fields_ = [("status", C.c_int32), ("l", C.c_int32), ("n_candidates", C.c_int32), ("_pad", C.c_int32),
+                ("excitation_var", C.c_double), ("relative_R", C.c_double * 9), ("relative_T", C.c_double * 3),
+                ("n_corres", C.c_int32 * _W), ("ransac_iters", C.c_int32 * _W), ("ransac_inliers", C.c_int32 * _W),
+                ("recover_inliers", C.c_int32 * _W), ("solution", C.c_int32 * _W), ("parallax", C.c_double * _W)]
+
+    def arr(self, name):
+        return np.ctypeslib.as_array(getattr(self, name)).copy()
+
+
+def _bind_relpose(lib):
+    if getattr(lib, "_relpose_bound", False):
+        return
+    lib.isv_internal_relpose_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(isv_sfm_problem_t)),
+                                               C.POINTER(isv_relpose_result_t), C.POINTER(C.POINTER(C.c_int32))]
+    lib.isv_internal_relpose_batch.restype = C.c_int
+    lib.isv_internal_relpose_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.isv_internal_relpose_last_ms.restype = C.c_int
+    lib._relpose_bound = True
+
+
+def apply_relpose(res, sp):
+    """relativePose's outputs (l, relative_R, relative_T) of an OK result into the SfM problem it was computed from"""
+    sp.c.l = res.l
+    sp.c.relative_R[:] = list(res.relative_R)
+    sp.c.relative_T[:] = list(res.relative_T)
+
+
+def relpose_batch(be, problems, write=False, masks=False):
+    """isv_internal_relpose_batch on the backend handle `be`; returns the results, and with masks=True also a list of
+    per-track inlier masks (int32 [n_tracks]: 1 / 0 for the chosen pair's correspondences, -1 elsewhere).  write=True copies
+    l / relative_R / relative_T of every OK result into its problem (apply_relpose)."""
+    lib = be.lib
+    _bind_relpose(lib)
+    n = len(problems)
+    ptrs = (C.POINTER(isv_sfm_problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
+    res = (isv_relpose_result_t * max(n, 1))()
+    mk, mptr = None, None
+    if masks:
+        mk = [np.full(max(p.c.n_tracks, 1), -1, dtype=np.int32) for p in problems]
+        mptr = (C.POINTER(C.c_int32) * max(n, 1))(*[m.ctypes.data_as(C.POINTER(C.c_int32)) for m in mk])
+    rc = lib.isv_internal_relpose_batch(be.h, n, ptrs, res, mptr)
+    if rc != 0:
+        raise backend.BackendError(f"isv_internal_relpose_batch: {backend.STATUS.get(rc, rc)}: {lib.isv_backend_last_error(be.h)}")
+    out = [res[i] for i in range(n)]
+    if write:
+        for r, p in zip(out, problems):
+            if r.status == 0:
+                apply_relpose(r, p)
+    return (out, [m[:p.c.n_tracks] for m, p in zip(mk, problems)]) if masks else out
+
+
+def relpose_last_ms(be):
+    """(whole call, kernel) milliseconds of the last relpose_batch on this handle"""
+    _bind_relpose(be.lib)
+    out = (C.c_double * 2)()
+    be.lib.isv_internal_relpose_last_ms(be.h, out)
+    return out[0], out[1]
+
+
+def initial_structure_from_tracks_batch(be, sfm_problems, align_problems):
+    """initialStructure from tracks, pre-integrations and RIC: the relative-pose stage on every problem (its l / relative_R /
+    relative_T written into the problem), then initial_structure_batch (SfM, then alignment) on the problems whose relative
+    pose was found.  Returns (relpose results, SfM results, alignment results), with None where an earlier stage refused."""
+    rr = relpose_batch(be, sfm_problems, write=True)
+    ok = [i for i, r in enumerate(rr) if r.status == 0]
+    sr = [None] * len(sfm_problems)
+    ar = [None] * len(sfm_problems)
+    if ok:
+        s_ok, a_ok = initial_structure_batch(be, [sfm_problems[i] for i in ok], [align_problems[i] for i in ok])
+        for i, s, a in zip(ok, s_ok, a_ok):
+            sr[i], ar[i] = s, a
+    return rr, sr, ar
+
+
+def make_relpose_scene(seed=0, n_window=18, outliers=0.0, **kw):
+    """make_scene (same arguments; its output is unchanged) with `outliers`: that fraction of the tracks that reach the last
+    window frame get a mismatched last observation, a uniform point in [-0.6, 0.6]^2 from a stream of their own.  Far depths
+    (low parallax) are make_scene's `depth`.  truth["outliers"]: the indices of the corrupted tracks.  The tracks do not
+    depend on l, so make_relpose_scene(seed, l=found, ...) gives the truth for the l the stage finds."""
+    sp, ap = make_scene(seed=seed, n_window=n_window, **kw)
+    bad = []
+    if outliers > 0:
+        rng = synth.SplitMix64(0x0E1A7E000000 + seed)
+        last = sp.c.n_window - 1
+        reach = [j for j in range(sp.c.n_tracks) if sp.tracks[j].start_frame + sp.tracks[j].n_obs - 1 == last]
+        u = rng.uniform(3 * len(reach)).reshape(-1, 3)
+        bad = [j for j, r in zip(reach, u) if r[0] < outliers]
+        wl = sp.c.window_frame[last]
+        for j, r in zip(reach, u):
+            if r[0] >= outliers:
+                continue
+            T = sp.tracks[j]
+            k = T.obs_off + T.n_obs - 1
+            sp.obs[k] = (r[1] - 0.5) * 1.2, (r[2] - 0.5) * 1.2
+            a, b = sp.pt_off[wl], sp.pt_off[wl + 1]   # all_image_frame's copy of the same observation
+            hit = np.nonzero(sp.pt_id[a:b] == T.id)[0]
+            if hit.size:
+                sp.pt_uv[a + hit[0]] = sp.obs[k]
+    sp.truth["outliers"] = np.array(bad, dtype=np.int64)
+    return sp, ap
