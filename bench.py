@@ -18,6 +18,12 @@ per-window result records, device buffers, no host copy -- runs inside every tim
   --dump-outputs DIR  after the timed steps, rank 0 writes what the last step computed for its windows (states, landmark
                       depths, prior factors, solve summaries, marginalisation results) as DIR/<name>.npy, float64; the
                       synthetic inputs are seeded by window id, so two builds can be compared output for output
+  --full              also measure and check everything beside the headline (below); off by default
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line (metric, value, unit,
+ms_per_step, ...).  --full adds, in the same run: the CPU baseline (oracle/isv_oracle.c on this host; --no-cpu-baseline skips
+it), a profiled step with per-kernel times and the roofline figures, the check that the all-gather covered every rank's
+windows, the strong-scaling leg (N > 1), and on one GPU the secondary legs (--no-host-legs skips them): single window,
+config 2, the 128-window shard, N = 18, config 5, the pose graph, the device-resident replay and the host-buffer rates.
 """
 import argparse
 import ctypes as C
@@ -204,8 +210,10 @@ def main():
     ap.add_argument("--frames", type=int, default=11)
     ap.add_argument("--vo", type=int, default=5)
     ap.add_argument("--landmarks", type=int, default=300)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-legs", action="store_true", help="skip the untimed secondary legs (host-buffer rates, single window, config 2, N = 18, B = 128); used for the rocprofv3 passes so that their kernel statistics hold the benchmark's own launches only")
+    ap.add_argument("--full", action="store_true", help="also run the CPU baseline, the profiled step and roofline figures, the multi-rank checks and "
+                    "strong-scaling leg, and the secondary legs; a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-legs", action="store_true", help="with --full: skip the untimed secondary legs (host-buffer rates, single window, config 2, N = 18, B = 128)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
     if args.steps < 1:
@@ -247,7 +255,7 @@ def main():
     cfg0 = backend.abi.make_config(args.frames, args.vo, max_landmarks=args.landmarks, max_obs=max_obs, max_batch=W)
     # CPU baseline on rank 0 BEFORE the process group exists: the other ranks sleep in the rendezvous meanwhile
     cpu = None; cpu_lib = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu, cpu_lib = cpu_baseline(windows, cfg0, budget_s=10.0 if world == 1 else 5.0)
 
     dist = None
@@ -300,6 +308,31 @@ def main():
         dt = sharding.max_over_ranks(dt, dist, device="cpu" if rehearsal else f"cuda:{dev}")
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, be, windows, ids)
+
+    def headline():
+        Fw = Ftot / W
+        return {
+            "metric": "sliding-window solves/sec (11 KF, ~300 landmarks)", "value": world * W * args.steps / dt, "unit": "windows/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+            "ms_per_optimize_batched": 1e3 * dt / args.steps / W,
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{W} independent synthetic sliding windows per GPU (N={args.frames} KF, Nvo={args.vo}, L={args.landmarks} landmarks, F~{Fw:.0f} reprojection factors each; BASELINE config 4 batch of config-2 windows), full backendOptimization(): NUM_ITERATIONS=10 dogleg iterations + update() + double2vector + MargForward/MargBackward on every window"
+                                   + ("" if world == 1 else f"; + one RCCL all-gather of the {world * W} per-window result records ({rec * 8} B each) per step"),
+                       "windows_per_gpu": W, "windows_total": world * W, "frames": args.frames, "landmarks": args.landmarks, "factors_total": Ftot, "iterations_cap": 10,
+                       "parallelism": f"independent windows block-partitioned over {world} rank(s) ({args.scaling} scaling), no collective inside the solve"
+                                      + ("" if world == 1 else "; exchange step = ncclAllGather of the result records on device buffers"),
+                       "collective_backend": None if world == 1 else ("gloo (one-GPU rehearsal)" if rehearsal else "nccl (RCCL)")},
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: checks, secondary legs and per-kernel figures, none of them inside the timed steps --------------
     # what the collective really connected: every rank's (rank, device index), gathered over the same process group
     ranks_seen = None
     if world > 1:
@@ -608,9 +641,7 @@ def main():
         be2.close()
 
     if rank == 0:
-        ms_step = 1e3 * dt / args.steps
-        value = world * W * args.steps / dt
-        N, L = args.frames, args.landmarks
+        N = args.frames
         Fw = Ftot / W
         Lw = sum(w.L for w in windows) / W
         n_lin, n_bs, n_sw = max(int(cnt[0]), 1), max(int(cnt[1]), 1), max(int(cnt[2]), 1)
@@ -675,19 +706,10 @@ def main():
                               "k_dogleg<true>: back-substitution, dogleg step, candidate costs and TrustRegionMinimizer step control in one kernel"))
         sums = {solve_kernel: bs_ms, "k_proj_linearize<0>": lin_ms, "k_lin_gram": lin_ms, "k_sweep_mfma": sw_ms, "k_rank1_mfma": r1_ms, "k_dogleg": dg_ms + (sc_ms if fused_control else 0), "k_step_control": sc_ms}
         dominant = max(roofs, key=lambda r: sums[r["kernel"]])
-        total_w = world * W
-        out = {
-            "metric": "sliding-window solves/sec (11 KF, ~300 landmarks)", "value": value, "unit": "windows/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "ms_per_optimize_batched": ms_step / W,
+        out = headline()
+        out["config"]["ranks_seen_by_the_collective"] = ranks_seen
+        out.update({
             "ms_per_optimize_single_window": extra.get("ms_per_optimize_single_window"),      # one resident window on a second handle, HIP events
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{W} independent synthetic sliding windows per GPU (N={N} KF, Nvo={args.vo}, L={L} landmarks, F~{Fw:.0f} reprojection factors each; BASELINE config 4 batch of config-2 windows), full backendOptimization(): NUM_ITERATIONS=10 dogleg iterations + update() + double2vector + MargForward/MargBackward on every window"
-                                   + ("" if world == 1 else f"; + one RCCL all-gather of the {total_w} per-window result records ({rec * 8} B each) per step"),
-                       "windows_per_gpu": W, "windows_total": total_w, "frames": N, "landmarks": L, "factors_total": Ftot, "iterations_cap": 10,
-                       "parallelism": f"independent windows block-partitioned over {world} rank(s) ({args.scaling} scaling), no collective inside the solve"
-                                      + ("" if world == 1 else "; exchange step = ncclAllGather of the result records on device buffers"),
-                       "ranks_seen_by_the_collective": ranks_seen, "collective_backend": None if world == 1 else ("gloo (one-GPU rehearsal)" if rehearsal else "nccl (RCCL)")},
             "roofline": dominant, "roofline_by_kernel": roofs,
             "host_buffers_inclusive": None if t_incl is None else {
                 "value": W / t_incl, "unit": "windows/s", "ms_per_batch": 1e3 * t_incl,
@@ -699,10 +721,10 @@ def main():
                           "dogleg_sum": dg_ms, "step_control_sum": sc_ms, "window_iterations": win_iters},
             "cpu_baseline": cpu,
             # SURVEY 8d / BASELINE.md 3 promise a stock-Ceres cross-check "if find_package(Ceres) succeeds on the GPU box": probed in
-            # round 3 (`find / -name ceres.h -o -path '*eigen3/Eigen/Dense' -o -name so3.hpp`: nothing; gpurun_out/r3_probe) -- the
-            # MI355X image has no Eigen, Ceres or Sophus either, so the oracle stays unpinned by the reference
+            # round 3 (`find / -name ceres.h -o -path '*eigen3/Eigen/Dense' -o -name so3.hpp`: nothing) -- the MI355X image has no
+            # Eigen, Ceres or Sophus either, so the oracle stays unpinned by the reference
             "ceres": "unavailable",
-        }
+        })
         if strong_leg is not None:
             out["strong_scaling_config4"] = strong_leg
         for k in ("config2_single_window_linearize", "strong_scaling_shard", "reference_shape_n18_vo8", "stress_config5", "device_resident_replay", "pose_graph_optimisation"):

@@ -7,7 +7,7 @@ def run(env, reps=3):
     best=None
     for _ in range(reps):
         e=dict(os.environ, **env)
-        out=subprocess.run([sys.executable,"bench.py","--steps","80","--no-cpu-baseline","--no-host-legs"],capture_output=True,text=True,env=e)
+        out=subprocess.run([sys.executable,"bench.py","--full","--steps","80","--no-cpu-baseline","--no-host-legs"],capture_output=True,text=True,env=e)
         try:
             d=json.loads(out.stdout.strip().splitlines()[-1])
         except Exception:

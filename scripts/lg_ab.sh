@@ -7,8 +7,8 @@ ISVINS_LIB=$PWD/scratch_libs/lib_head.so timeout -k 10 300 python scripts/ab_bit
 diff $out/bits_new.txt $out/bits_head.txt > $out/bits_diff.txt && echo BITS_SAME | tee -a $out/bits_diff.txt
 for mode in two one; do
   [ $mode = one ] && export ISV_ONE_STREAM=1
-  timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 > $out/bench_${mode}_new.json 2> $out/bench_${mode}_new.err
-  ISVINS_LIB=$PWD/scratch_libs/lib_head.so timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 > $out/bench_${mode}_head.json 2> $out/bench_${mode}_head.err
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 > $out/bench_${mode}_new.json 2> $out/bench_${mode}_new.err
+  ISVINS_LIB=$PWD/scratch_libs/lib_head.so timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 > $out/bench_${mode}_head.json 2> $out/bench_${mode}_head.err
 done
 python - <<'PY' | tee $out/summary.txt
 import json

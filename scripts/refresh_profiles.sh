@@ -8,7 +8,7 @@ RN=${1:-r05}; W=${2:-1024}; PART=${3:-AB}
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_$RN
 mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-host-legs --windows $W"
+B="python3 bench.py --full --no-cpu-baseline --no-host-legs --windows $W"
 if [[ $PART == *A* ]]; then
 # 1. kernel-trace stats of the bench command (the launches of the benchmark only)
 rocprofv3 --kernel-trace --stats -d $O/bench -o bench --output-format csv -- $B --steps 5 --warmup 2 > $O/bench_under_rocprof.json 2> $O/bench.err
@@ -48,9 +48,9 @@ rocprofv3 --kernel-trace --stats -d $O/replay -o replay --output-format csv -- .
 cp $O/replay/replay_kernel_stats.csv $O/${RN}_resident_replay_256seq_kernel_stats.csv
 # 8. the bench line itself and the two-rank rehearsal of the multi-GPU path on this one GPU (gloo stands in for RCCL);
 #    only the JSON line goes into the artefact (gloo's connection messages used to land in the .json)
-python3 bench.py > $O/bench_plain.out 2> $O/bench_plain.err
-grep '^{' $O/bench_plain.out | tail -1 > $O/${RN}_bench_1gpu.json
-ISV_BENCH_REHEARSAL=1 python3 bench.py --gpus 2 --windows 512 --no-host-legs --no-cpu-baseline --steps 50 > $O/rehearsal.out 2> $O/rehearsal.err
+python3 bench.py --full > $O/bench_full.out 2> $O/bench_full.err
+grep '^{' $O/bench_full.out | tail -1 > $O/${RN}_bench_1gpu.json
+ISV_BENCH_REHEARSAL=1 python3 bench.py --full --gpus 2 --windows 512 --no-host-legs --no-cpu-baseline --steps 50 > $O/rehearsal.out 2> $O/rehearsal.err
 grep '^{' $O/rehearsal.out | tail -1 > $O/${RN}_2rank_rehearsal.json
 # 9. kernel boundary against grid barrier (what a persistent single-window kernel would have to beat) and the launch chain of one window
 hipcc -O3 --offload-arch=gfx950 -o /tmp/launch_vs_barrier scripts/launch_vs_barrier.hip && timeout -k 10 120 /tmp/launch_vs_barrier > $O/${RN}_launch_vs_barrier.json
