@@ -357,7 +357,8 @@ int  isv_backend_seq_marg(isv_backend_t *h, int32_t slot, isv_marg_result_t *out
 
 /* last optimize: [0] k_lin_gram (or k_proj_linearize<0>) launches, [1] k_build_solve* launches, [2] k_rank1_mfma launches,
  * [3] window-iterations that were linearised and solved (windows gated out of an iteration do no work),
- * [4] 1 when the fused k_lin_gram ran (no Jacobian strips), [5] 1 when k_dogleg<true> carried the step control */
+ * [4] 1 when the fused k_lin_gram ran (no Jacobian strips), [5] 1 when k_dogleg<true> carried the step control,
+ * [6] 1 when k_build_solve_st ran, [7] the split landmark elimination's groups per window (0: not split) */
 int  isv_batch_last_counts(isv_backend_t *h, int64_t out[8]);
 
 #ifdef __cplusplus

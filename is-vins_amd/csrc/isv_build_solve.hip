@@ -8,12 +8,12 @@
 // Gauss-Newton retry loop (dogleg_strategy.cc ComputeGaussNewtonStep) are folded in.
 //
 // Data layout: the reduced matrix T (15N x 15N, symmetric) is kept as the lower block triangle of
-// 15x15 blocks (one block row per frame), N(N+1)/2 * 225 doubles -- 118.8 KB for N = 11, resident
-// in LDS for the whole build + factorisation; larger windows (reference N = 18, stress N = 20) use
-// the same code on an L2-resident global scratch.  Reprojection strips are streamed through LDS in
-// chunks of <= 64 factors (whole landmarks).  Accumulation is OWNER-COMPUTES: wavefront `a` owns
-// block column `a` (frame a), so every T entry is summed by one lane in landmark order -- bitwise
-// reproducible, no atomics.
+// 15x15 blocks (one block row per frame), N(N+1)/2 * 225 doubles, in an L2-resident global scratch
+// (d.Tglob).  This kernel serves the handles the LDS-resident solves (isv_build_solve_sb.hip,
+// isv_build_solve_st.hip) do not take (d.lds_T == 0: windows beyond 20 frames, see isv_solver_alloc).
+// Reprojection strips are streamed through LDS in chunks of <= 64 factors (whole landmarks).
+// Accumulation is OWNER-COMPUTES: wavefront `a` owns block column `a` (frame a), so every T entry is
+// summed by one lane in landmark order -- bitwise reproducible, no atomics.
 //
 // Scaling algebra: with Jacobi scaling Sc and LM diagonal mu D^2, Ceres solves in scaled space
 //   (Sc H Sc + mu D^2) y = Sc g.   Writing c_l = s_l^2 / (s_l^2 E_l + mu D_l^2) for landmark l, the
@@ -64,15 +64,14 @@ DEV void accum_dense(double *T, double *g, double *hdiag, const double *Jd, cons
     }
 }
 
-template <bool LDS_T>
 __global__ __launch_bounds__(BS_THREADS) void k_build_solve(DevBatch d) {
     extern __shared__ __align__(16) double lds[];
     const int w = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
     SolveState &st = d.st[w];
     if (st.termination != ISV_TERM_RUNNING || !st.need_linearize) return;
     const int N = d.N, n = 15 * N, nblkT = N * (N + 1) / 2 * 225;
-    double *T = LDS_T ? lds : d.Tglob + (size_t)w * nblkT;
-    double *p = LDS_T ? lds + nblkT : lds;
+    double *T = d.Tglob + (size_t)w * nblkT;
+    double *p = lds;
     double *g = p; p += n;            // unscaled gradient J^T r (pose part)
     double *bs = p; p += n;           // Schur rhs correction  -sum_l c_l w_l g_l
     double *hdiag = p; p += n;        // diag(H_pp) before elimination
@@ -477,11 +476,9 @@ __global__ __launch_bounds__(BS_THREADS) void k_build_solve(DevBatch d) {
         if (st.gmax <= 1e-10) st.termination = ISV_TERM_GRADIENT_TOL;
     }
 }
-template __global__ void k_build_solve<true>(DevBatch);
-template __global__ void k_build_solve<false>(DevBatch);
 
-size_t build_solve_lds_bytes(int N, bool lds_T) {
-    const size_t n = 15 * (size_t)N, nblkT = (size_t)N * (N + 1) / 2 * 225;
-    size_t dbl = (lds_T ? nblkT : 0) + 7 * n + BS_THREADS + CH * 28 + 2 * CH * 6 + 2 * CH + 225;
+size_t build_solve_lds_bytes(int N) {
+    const size_t n = 15 * (size_t)N;
+    size_t dbl = 7 * n + BS_THREADS + CH * 28 + 2 * CH * 6 + 2 * CH + 225;
     return dbl * sizeof(double) + 64 * sizeof(int);
 }

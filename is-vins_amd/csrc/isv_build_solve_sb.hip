@@ -1259,6 +1259,7 @@ __global__ __launch_bounds__(LS, 2) void k_lin_gram_chain(DevBatch d) {
 // k_pose_dogleg (round 5): the pose half of the split solve, the dogleg step and the step control of a window in ONE launch -- three stages
 // of one workgroup per window that followed each other as separate launches (~4 us each on this GPU for a small batch, plus the reload
 // of what the previous stage had in LDS).  The same routines in the same order: bit for bit the three-launch sequence.
+// Windows of up to 11 frames only (BIG = false): the 18-frame form loses to the two launches.
 template <bool BIG, int NC, bool EX>
 __global__ __launch_bounds__(LS, 2) void k_pose_dogleg(DevBatch d) {
     extern __shared__ __align__(16) double lds[];
@@ -1274,11 +1275,10 @@ __global__ __launch_bounds__(LS, 2) void k_pose_dogleg(DevBatch d) {
     __syncthreads();                                  // candidate states, per-factor costs and model pieces of this window are written
     step_control_body<true, EX>(d, blockIdx.x, threadIdx.x, lds, red, s_accept);
 }
+// (every form the solver's per-handle kernel table can name: isv_solver_alloc)
 template __global__ void k_pose_dogleg<false, 11, false>(DevBatch);
 template __global__ void k_pose_dogleg<false, 0, false>(DevBatch);
-template __global__ void k_pose_dogleg<true, 0, false>(DevBatch);
 template __global__ void k_pose_dogleg<false, 0, true>(DevBatch);
-template __global__ void k_pose_dogleg<true, 0, true>(DevBatch);
 template __global__ void k_lin_gram_chain<false, false, 0, 0>(DevBatch);
 template __global__ void k_lin_gram_chain<false, false, 11, 0>(DevBatch);
 template __global__ void k_lin_gram_chain<false, true, 0, 0>(DevBatch);

@@ -16,8 +16,26 @@ template <bool JAC> __global__ void k_prior_linearize(DevBatch d, const double *
 __global__ void k_cost_reduce(DevBatch d, const double *fcost, const double *imu_cost, const double *prior_cost, double *out, int gate);
 
 // solver stage (isv_solver.hip)
-// host-side launch parameters of a handle: device figures and environment hooks, read ONCE in isv_solver_alloc (the
-// kernel VARIANT of a launch is then chosen from these and the uploaded batch: see isv_solver_enqueue)
+// one entry of a handle's kernel table: the instantiation, its threads per workgroup, and the dynamic LDS its attribute is
+// raised to (0: not raised)
+struct SolverKernel { const void *fn = nullptr; unsigned threads = 0; size_t lds = 0; };
+// the roles of the table (SolverHost::kern).  isv_solver_alloc fills them ONCE per handle from its constants (N, est_ex,
+// nt = wd_ld / 16, lds_T, solve_st, chain_split, ISV_GENERIC_N, ISV_NO_POSE_DOGLEG): the compile-time window lengths (N = 11,
+// the st kernel's N = 18) are chosen there and nowhere else.  An empty role (fn == nullptr) is one the handle never launches.
+enum SolverRole {
+    KR_SOLVE,                 // the whole reduced solve: k_build_solve_sb MODE 0, k_build_solve_st, or the dense k_build_solve (!lds_T)
+    KR_CHAIN, KR_POSE,        // chain_split handles: the chain half (k_build_solve_sb MODE 1) and the pose half (MODE 2)
+    KR_LIN_GRAM_CHAIN,        // chain_split handles: k_lin_gram_chain ...
+    KR_LIN_GRAM_CHAIN_R1,     // ... and its form with the rank-1 downdates in the same workgroup (NT = 7; N > 11, no extrinsic)
+    KR_POSE_DOGLEG,           // chain_split handles of N <= 11: k_pose_dogleg
+    KR_RANK1, KR_RANK1_SPLIT, KR_SCHUR_SPLIT,   // the landmark elimination for this nt (the split pair only with d.r1_part)
+    KR_LIN_GRAM, KR_LIN_GRAM_SMALL,             // k_lin_gram with LG_WAVES / LG_WAVES_SMALL wavefronts
+    KR_DOGLEG, KR_DOGLEG_CONTROL, KR_STEP_CONTROL,   // k_dogleg<false / true, EX>, k_step_control<true, EX>
+    KR_SWEEP, KR_FRONT,       // k_sweep_mfma (lds_T), k_front (chain_split)
+    KR_COUNT
+};
+// host-side launch parameters of a handle: device figures, environment hooks and the kernel table, set ONCE in isv_solver_alloc
+// (isv_solver_enqueue then chooses among these per uploaded batch)
 struct SolverHost {
     int n_cus = 0;                    // compute units of the handle's device
     size_t cap_batch = 0;             // the handle's max_batch: kernel VARIANTS whose results differ in the last bits (k_build_solve_st, the split
@@ -26,11 +44,10 @@ struct SolverHost {
     int dogleg_per_cu_regs = 0;       // workgroups of k_dogleg<true, EX> per CU by registers (the LDS bound is applied per enqueue)
     bool one_stream = false;          // ISV_ONE_STREAM: diagnostics, everything on one stream
     bool split_control = false;       // ISV_SPLIT_CONTROL: k_dogleg<false> + k_step_control
-    bool generic_n = false;           // ISV_GENERIC_N: run-time-N instantiation of k_build_solve_sb for every N
+    bool generic_n = false;           // ISV_GENERIC_N: the run-time-N instantiations in the kernel table for every N
     bool lg_batch_waves = false;      // ISV_LG_BATCH_WAVES: never the eight-wavefront k_lin_gram
     bool debug_sw_global = false;     // ISV_DEBUG_SW_GLOBAL: pair partials in the global scratch for every launch
     bool legacy_visual = false;       // ISV_LEGACY_VISUAL: the unfused k_proj_linearize<0> + k_sweep_mfma pair
-    bool no_persistent = false;       // ISV_NO_PERSISTENT: never the one-launch solve of small batches
     bool sw_global_ok = false;        // the handle's windows are long enough (or ISV_DEBUG_SW_GLOBAL) for the pair partials in global memory
     bool solve_st = false;            // this handle runs k_build_solve_st (four windows per CU; chosen from the handle's max_batch, ISV_SOLVE_ST=0/1 forces)
     bool chain_split = false;         // this handle splits the reduced-system solve into the chain kernel (side stream) and the pose kernel (k_build_solve_sb MODE 1 / 2):
@@ -42,6 +59,7 @@ struct SolverHost {
     bool no_update = false;           // ISV_DEBUG_NO_UPDATE (sensitivity study, tests/test_sequence_long.py; the oracle has the same
                                       // hook): skip the update() of the prior factors' pseudo-measurements after the solve
                                       // (src/estimator.cpp:1133-1144).  NOT the reference's behaviour.
+    SolverKernel kern[KR_COUNT];      // the kernel of each role on this handle
 };
 int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, std::vector<void *> &allocs, std::string &err);
 int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStream_t st2, hipEvent_t *fj, int64_t *counts, hipEvent_t *prof_ev, std::string &err);
@@ -62,6 +80,10 @@ __global__ void k_schur_fold(DevBatch d, int GrMax, int NT, int from_partials);
 __global__ void k_imu_raw(DevBatch d, const double *pose_src, const double *sb_src, int gate);
 __global__ void k_imu_weight(DevBatch d, double *cost_out, int gate);
 #define ISV_PROF_FAMILIES 6      // 0 = k_proj_linearize<0>, 1 = k_sweep_mfma, 2 = k_rank1_mfma, 3 = k_build_solve*, 4 = k_dogleg, 5 = k_step_control
+// the launch counters of an optimize (isv_batch_last_counts): linearisations, reduced solves and landmark eliminations per slot,
+// window-iterations (filled from d.act by isv_batch_last_counts), 1 when the fused k_lin_gram ran, 1 when the step control ran
+// in the dogleg's workgroup, 1 when k_build_solve_st ran, the split elimination's groups per window (0: not split)
+enum { ISV_CNT_LINEARIZE, ISV_CNT_SOLVE, ISV_CNT_ELIM, ISV_CNT_WINDOW_ITERS, ISV_CNT_FUSED_VISUAL, ISV_CNT_FUSED_CONTROL, ISV_CNT_SOLVE_ST, ISV_CNT_SPLIT_GROUPS };
 // pinned staging for the result records (capacity max_batch): asynchronous device-to-host copies into pageable
 // memory go through the runtime's own staging and may complete lazily, which stalled the NEXT upload by 13-30 ms for
 // batches above ~1 MB of records

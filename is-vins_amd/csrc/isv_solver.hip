@@ -11,6 +11,7 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <mutex>
 #include "isv_kernels.h"
 #include "isv_device_math.h"
@@ -18,7 +19,7 @@
 #include "isv_prior_factor.h"
 #include "isv_imu_factor.h"
 
-extern size_t build_solve_lds_bytes(int N, bool lds_T);
+extern size_t build_solve_lds_bytes(int N);
 template <bool BIG, int NC, int MODE> __global__ void k_build_solve_sb(DevBatch d);
 extern size_t build_solve_sb_bytes(int N, int prior_H_sz);
 extern size_t build_solve_cs_doubles(int N);
@@ -40,7 +41,7 @@ __global__ void k_marg_clear(DevBatch d);
 template <int MTF> __global__ void k_marg_fwd(DevBatch d);
 template <int PART> __global__ void k_marg_bwd(DevBatch d);
 template <int NC> __global__ void k_marg_jacobi(DevBatch d);
-template <bool LDS_T> __global__ void k_build_solve(DevBatch d);
+__global__ void k_build_solve(DevBatch d);
 
 // ------------------------------------------------------------------------------------------
 __global__ void k_init_state(DevBatch d) {
@@ -250,12 +251,20 @@ static size_t dogleg_lds_bytes(const DevBatch &d) {
 static size_t step_control_lds_bytes(const DevBatch &d) { return ((size_t)30 * d.N + 12 + (d.ctl_stage_lm ? 6 * (size_t)d.lg_lcap : 0)) * sizeof(double); }
 #define ISV_CTL_STAGE_MAX_BYTES ((size_t)36 * 1024)      // staged only while four workgroups still share a CU
 
-// workgroups of kernel `fn` (threads per workgroup, dynamic LDS bytes) the current device holds at once
-static size_t resident_workgroups(const void *fn, int threads, size_t lds) {
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return (size_t)per_cu * (size_t)cus;
+// the reduced-system kernels: N = 11 compiled in (unless ISV_GENERIC_N), else run-time N; BIG beyond 11 frames
+template <int MODE> static const void *solve_sb_kernel(int N, bool generic_n) {
+    if (N == 11 && !generic_n) return (const void *)k_build_solve_sb<false, 11, MODE>;
+    return N <= 11 ? (const void *)k_build_solve_sb<false, 0, MODE> : (const void *)k_build_solve_sb<true, 0, MODE>;
+}
+// the landmark elimination's kernels for NT 16-column tiles: TPW tiles per wavefront, 64 * ceil(NT (NT + 1) / 2 / TPW) threads
+template <int NT> static void set_rank1_kernels(SolverKernel *k, bool ex, bool split, size_t lds_r1, size_t lds_sp) {
+    constexpr int TPW = NT <= 5 ? 1 : NT <= 7 ? 2 : 3;
+    constexpr unsigned threads = 64 * ((NT * (NT + 1) / 2 + TPW - 1) / TPW);
+    k[KR_RANK1] = {ex ? (const void *)k_rank1_mfma<NT, TPW, 64, 1, true> : (const void *)k_rank1_mfma<NT, TPW, 64, 1, false>, threads, lds_r1};
+    if (split) {
+        k[KR_RANK1_SPLIT] = {(const void *)k_rank1_split<NT, TPW>, threads, lds_r1};
+        k[KR_SCHUR_SPLIT] = {(const void *)k_schur_split<NT, TPW>, threads, lds_sp};
+    }
 }
 
 int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, std::vector<void *> &allocs, std::string &err) {
@@ -293,7 +302,7 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     hc.one_stream = getenv("ISV_ONE_STREAM") != nullptr; hc.split_control = getenv("ISV_SPLIT_CONTROL") != nullptr;
     hc.generic_n = getenv("ISV_GENERIC_N") != nullptr; hc.lg_batch_waves = getenv("ISV_LG_BATCH_WAVES") != nullptr;
     hc.debug_sw_global = getenv("ISV_DEBUG_SW_GLOBAL") != nullptr; hc.legacy_visual = getenv("ISV_LEGACY_VISUAL") != nullptr;
-    hc.no_persistent = getenv("ISV_NO_PERSISTENT") != nullptr; hc.no_split = getenv("ISV_NO_SPLIT") != nullptr;
+    hc.no_split = getenv("ISV_NO_SPLIT") != nullptr;
     hc.no_update = getenv("ISV_DEBUG_NO_UPDATE") != nullptr; hc.no_pose_dogleg = getenv("ISV_NO_POSE_DOGLEG") != nullptr;
     hc.marg_one_kernel = getenv("ISV_MARG_ONE_KERNEL") != nullptr; hc.marg_split = getenv("ISV_MARG_SPLIT") != nullptr;
     int dev0_ = 0;
@@ -346,76 +355,82 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     d.marg_scratch_sz = 26;
     TRYA(dal(&d.marg_scratch, L * 26, allocs, err));
     TRYA(dal(&d.marg_ws, B * ISV_MARG_WS, allocs, err));
-    int dev_ = 0;
-    HCHK(hipGetDevice(&dev_));
-    if (d.lds_T) {
-        // the attribute is per kernel (and device) and process-wide: handles of different shapes must not lower each other's value
-#define SETLDS(K, BYTES) do { static size_t cur_[64] = {}; std::lock_guard<std::mutex> lk_(g_lds_attr_mutex); if ((size_t)(BYTES) > cur_[dev_ & 63]) { HCHK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))); cur_[dev_ & 63] = (size_t)(BYTES); } } while (0)
-        SETLDS((k_rank1_mfma<1, 1, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<1, 1, 64, 1, true>), lds_r1); SETLDS((k_rank1_mfma<2, 1, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<2, 1, 64, 1, true>), lds_r1); SETLDS((k_rank1_mfma<3, 1, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<3, 1, 64, 1, true>), lds_r1);
-        SETLDS((k_rank1_mfma<4, 1, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<4, 1, 64, 1, true>), lds_r1); SETLDS((k_rank1_mfma<5, 1, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<5, 1, 64, 1, true>), lds_r1); SETLDS((k_rank1_mfma<6, 2, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<6, 2, 64, 1, true>), lds_r1);
-        SETLDS((k_rank1_mfma<7, 2, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<7, 2, 64, 1, true>), lds_r1); SETLDS((k_rank1_mfma<8, 3, 64, 1, false>), lds_r1); SETLDS((k_rank1_mfma<8, 3, 64, 1, true>), lds_r1);
-        SETLDS(k_sweep_mfma, lds_sw);
-        if (d.r1_part) {
-            const size_t lds_sp = lds_r1 > (2 * n_pairs + 2) * sizeof(int) ? lds_r1 : (2 * n_pairs + 2) * sizeof(int);
-            SETLDS((k_schur_split<1, 1>), lds_sp); SETLDS((k_schur_split<2, 1>), lds_sp); SETLDS((k_schur_split<3, 1>), lds_sp); SETLDS((k_schur_split<4, 1>), lds_sp);
-            SETLDS((k_schur_split<5, 1>), lds_sp); SETLDS((k_schur_split<6, 2>), lds_sp); SETLDS((k_schur_split<7, 2>), lds_sp); SETLDS((k_schur_split<8, 3>), lds_sp);
-            SETLDS((k_rank1_split<1, 1>), lds_r1); SETLDS((k_rank1_split<2, 1>), lds_r1); SETLDS((k_rank1_split<3, 1>), lds_r1); SETLDS((k_rank1_split<4, 1>), lds_r1);
-            SETLDS((k_rank1_split<5, 1>), lds_r1); SETLDS((k_rank1_split<6, 2>), lds_r1); SETLDS((k_rank1_split<7, 2>), lds_r1); SETLDS((k_rank1_split<8, 3>), lds_r1);
-        }
-        {   // k_lin_gram: up to the whole CU (the launch sizes its LDS from the uploaded windows: isv_batch_upload)
-            auto cap = [&](int waves) { const size_t b = lin_gram_lds_bytes(d.Nr, true, d.est_ex != 0, waves, d.max_lm); return b < ISV_LDS_PER_CU ? b : ISV_LDS_PER_CU; };
-            if (d.est_ex) { SETLDS((k_lin_gram<true, LG_WAVES>), cap(LG_WAVES)); SETLDS((k_lin_gram<true, LG_WAVES_SMALL>), cap(LG_WAVES_SMALL)); }
-            else { SETLDS((k_lin_gram<false, LG_WAVES>), cap(LG_WAVES)); SETLDS((k_lin_gram<false, LG_WAVES_SMALL>), cap(LG_WAVES_SMALL)); }
-        }
-        if (hc.solve_st) {
-            const size_t lds_st = build_solve_st_bytes(d.N, d.prior_H_sz);
-            if (d.N == 11) SETLDS((k_build_solve_st<false, 11>), lds_st);
-            if (d.N <= 11) SETLDS((k_build_solve_st<false, 0>), lds_st);
-            if (d.N > 11) SETLDS((k_build_solve_st<true, 0>), lds_st);
-            if (d.N == 18) SETLDS((k_build_solve_st<true, 18>), lds_st);
-        }
-        if (d.N == 11) SETLDS((k_build_solve_sb<false, 11, 0>), lds_sb);
-        if (d.N <= 11) SETLDS((k_build_solve_sb<false, 0, 0>), lds_sb);
-        if (d.N > 11) SETLDS((k_build_solve_sb<true, 0, 0>), lds_sb);
-        if (hc.chain_split) {
-            SETLDS(k_front, front_lds_bytes(d.N, d.n_prior_slots));
-            {   // k_lin_gram_chain: the larger of its two roles' needs
-                const size_t lg = lin_gram_lds_bytes(d.Nr, true, d.est_ex != 0, LG_WAVES_SMALL, d.max_lm);
-                size_t both = lg > lds_sb ? lg : lds_sb;
-                if (both < lds_r1) both = lds_r1;
-                if (both > ISV_LDS_PER_CU) both = ISV_LDS_PER_CU;
-                if (d.est_ex) { if (d.N <= 11) SETLDS((k_lin_gram_chain<true, false, 0, 0>), both); else SETLDS((k_lin_gram_chain<true, true, 0, 0>), both); }
-                else if (d.N == 11) { SETLDS((k_lin_gram_chain<false, false, 11, 0>), both); SETLDS((k_lin_gram_chain<false, false, 0, 0>), both); }
-                else if (d.N < 11) SETLDS((k_lin_gram_chain<false, false, 0, 0>), both);
-                else { SETLDS((k_lin_gram_chain<false, true, 0, 0>), both); SETLDS((k_lin_gram_chain<false, true, 0, 7>), both); }
-            }
-            {   // k_pose_dogleg: the pose half's LDS or the dogleg / step control's, whichever is larger (the latter is sized per enqueue: up to a CU)
-                const size_t pd = ISV_LDS_PER_CU - 4096;
-                if (d.est_ex) { if (d.N <= 11) SETLDS((k_pose_dogleg<false, 0, true>), pd); else SETLDS((k_pose_dogleg<true, 0, true>), pd); }
-                else if (d.N == 11) { SETLDS((k_pose_dogleg<false, 11, false>), pd); SETLDS((k_pose_dogleg<false, 0, false>), pd); }
-                else if (d.N < 11) SETLDS((k_pose_dogleg<false, 0, false>), pd);
-                else SETLDS((k_pose_dogleg<true, 0, false>), pd);
-            }
-            if (d.N == 11) { SETLDS((k_build_solve_sb<false, 11, 1>), lds_sb); SETLDS((k_build_solve_sb<false, 11, 2>), lds_sb); }
-            if (d.N <= 11) { SETLDS((k_build_solve_sb<false, 0, 1>), lds_sb); SETLDS((k_build_solve_sb<false, 0, 2>), lds_sb); }
-            if (d.N > 11) { SETLDS((k_build_solve_sb<true, 0, 1>), lds_sb); SETLDS((k_build_solve_sb<true, 0, 2>), lds_sb); }
-        }
-#undef SETLDS
-    }
+    // the kernel table: the instantiation of every role this handle can launch
+    SolverKernel *k = hc.kern;
+    const bool ex = d.est_ex != 0, gn = hc.generic_n;
+    const int N = d.N;
+    k[KR_DOGLEG] = {ex ? (const void *)k_dogleg<false, true> : (const void *)k_dogleg<false, false>, 256, 0};
+    k[KR_DOGLEG_CONTROL] = {ex ? (const void *)k_dogleg<true, true> : (const void *)k_dogleg<true, false>, 256, 0};
+    k[KR_STEP_CONTROL] = {ex ? (const void *)k_step_control<true, true> : (const void *)k_step_control<true, false>, 256, 0};
+    if (!d.lds_T) k[KR_SOLVE] = {(const void *)k_build_solve, 512, build_solve_lds_bytes(N)};
     else {
-        static size_t cur_bs[64] = {};
-        std::lock_guard<std::mutex> lk(g_lds_attr_mutex);
-        const size_t want = build_solve_lds_bytes(d.N, false);
-        if (want > cur_bs[dev_ & 63]) { HCHK(hipFuncSetAttribute((const void *)k_build_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)); cur_bs[dev_ & 63] = want; }
+        k[KR_SWEEP] = {(const void *)k_sweep_mfma, 64 * ISV_SWEEP_WAVES, lds_sw};
+        // lds_T: wd_ld <= 128, so 1 <= nt <= 8
+        static void (*const rank1_for_nt[8])(SolverKernel *, bool, bool, size_t, size_t) = {
+            set_rank1_kernels<1>, set_rank1_kernels<2>, set_rank1_kernels<3>, set_rank1_kernels<4>,
+            set_rank1_kernels<5>, set_rank1_kernels<6>, set_rank1_kernels<7>, set_rank1_kernels<8>};
+        const size_t lds_sp = lds_r1 > (2 * n_pairs + 2) * sizeof(int) ? lds_r1 : (2 * n_pairs + 2) * sizeof(int);
+        rank1_for_nt[d.wd_ld / 16 - 1](k, ex, d.r1_part != nullptr, lds_r1, lds_sp);
+        // k_lin_gram: up to the whole CU (the launch sizes its LDS from the uploaded windows: isv_batch_upload)
+        auto lg_cap = [&](int waves) { const size_t b = lin_gram_lds_bytes(d.Nr, true, ex, waves, d.max_lm); return b < ISV_LDS_PER_CU ? b : ISV_LDS_PER_CU; };
+        k[KR_LIN_GRAM] = {ex ? (const void *)k_lin_gram<true, LG_WAVES> : (const void *)k_lin_gram<false, LG_WAVES>, 64 * LG_WAVES, lg_cap(LG_WAVES)};
+        k[KR_LIN_GRAM_SMALL] = {ex ? (const void *)k_lin_gram<true, LG_WAVES_SMALL> : (const void *)k_lin_gram<false, LG_WAVES_SMALL>, 64 * LG_WAVES_SMALL, lg_cap(LG_WAVES_SMALL)};
+        if (hc.solve_st) {
+            // (the reference's ALL_BUF_SIZE as a compile-time constant: 404 -> 357 us per launch, 1024 windows 10.27 -> 9.87 ms.  The same for
+            //  k_build_solve_sb<true, 18> spills 62 registers and is SLOWER for the single window it serves: 2.54 against 2.48 ms; not instantiated)
+            const void *fn = N == 11 && !gn ? (const void *)k_build_solve_st<false, 11> : N <= 11 ? (const void *)k_build_solve_st<false, 0>
+                           : N == 18 && !gn ? (const void *)k_build_solve_st<true, 18> : (const void *)k_build_solve_st<true, 0>;
+            k[KR_SOLVE] = {fn, N <= 11 ? 256u : 512u, build_solve_st_bytes(N, d.prior_H_sz)};      // (long windows: eight wavefronts, two windows per CU)
+        } else if (!hc.chain_split) k[KR_SOLVE] = {solve_sb_kernel<0>(N, gn), 512, lds_sb};
+        else {
+            k[KR_CHAIN] = {solve_sb_kernel<1>(N, gn), 512, lds_sb};
+            k[KR_POSE] = {solve_sb_kernel<2>(N, gn), 512, lds_sb};
+            k[KR_FRONT] = {(const void *)k_front, 512, front_lds_bytes(N, d.n_prior_slots)};
+            // k_lin_gram_chain: the larger of its two roles' needs
+            size_t lgc = lin_gram_lds_bytes(d.Nr, true, ex, LG_WAVES_SMALL, d.max_lm);
+            if (lgc < lds_sb) lgc = lds_sb;
+            if (lgc < lds_r1) lgc = lds_r1;
+            if (lgc > ISV_LDS_PER_CU) lgc = ISV_LDS_PER_CU;
+            const void *fn = ex ? (N <= 11 ? (const void *)k_lin_gram_chain<true, false, 0, 0> : (const void *)k_lin_gram_chain<true, true, 0, 0>)
+                           : N == 11 && !gn ? (const void *)k_lin_gram_chain<false, false, 11, 0>
+                           : N <= 11 ? (const void *)k_lin_gram_chain<false, false, 0, 0> : (const void *)k_lin_gram_chain<false, true, 0, 0>;
+            k[KR_LIN_GRAM_CHAIN] = {fn, 512, lgc};
+            // the rank-1 downdates in the same workgroup (the shapes instantiated for it)
+            if (!ex && !gn && N > 11 && d.wd_ld / 16 == 7 && lds_r1 <= ISV_LDS_PER_CU) k[KR_LIN_GRAM_CHAIN_R1] = {(const void *)k_lin_gram_chain<false, true, 0, 7>, 512, lgc};
+            // k_pose_dogleg: the pose half's LDS or the dogleg / step control's, whichever is larger (the latter is sized per enqueue: up to a CU).
+            // 11 frames and fewer only (measured: 128 windows of 11 frames 1.92 -> 1.86 ms; the 18-frame form LOSES -- 117 us against 70 + 37
+            // for the two launches, rocprofv3)
+            if (N <= 11 && !hc.no_pose_dogleg) {
+                const void *pd = ex ? (const void *)k_pose_dogleg<false, 0, true> : N == 11 && !gn ? (const void *)k_pose_dogleg<false, 11, false> : (const void *)k_pose_dogleg<false, 0, false>;
+                k[KR_POSE_DOGLEG] = {pd, 512, ISV_LDS_PER_CU - 4096};
+            }
+        }
     }
-    // device figures the per-launch variant choice needs (once per handle, not per isv_batch_optimize): hc.n_cus (above) and
+    // the dynamic-LDS attribute is per kernel and device and process-wide: handles of different shapes must not lower each other's value
     {
-        // k_dogleg<true, EX> by registers alone (a small dynamic LDS request); the LDS bound is applied per enqueue
+        static std::map<std::pair<const void *, int>, size_t> raised;
+        std::lock_guard<std::mutex> lk(g_lds_attr_mutex);
+        for (const SolverKernel &e : hc.kern) {
+            if (!e.lds) continue;
+            size_t &cur = raised[{e.fn, dev0_}];
+            if (e.lds > cur) { HCHK(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds)); cur = e.lds; }
+        }
+    }
+    // device figures the per-launch variant choice needs (once per handle, not per isv_batch_optimize): hc.n_cus (above) and the
+    // workgroups of k_dogleg<true, EX> per CU by registers alone (a small dynamic LDS request); the LDS bound is applied per enqueue
+    {
         int per_cu = 0;
-        if (d.lds_T && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, d.est_ex ? (const void *)k_dogleg<true, true> : (const void *)k_dogleg<true, false>, 256, 1024) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+        if (d.lds_T && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k[KR_DOGLEG_CONTROL].fn, 256, 1024) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
         hc.dogleg_per_cu_regs = per_cu;
     }
     return ISV_OK;
+}
+
+// launch table entry k with the arguments a: the runtime receives the same kernel handle as from hipLaunchKernelGGL of the
+// instantiation, and a failed launch surfaces at the enqueue's closing hipGetLastError like theirs
+template <typename... A> static void launch(const SolverKernel &k, dim3 grid, size_t lds, hipStream_t s, A... a) {
+    void *args[] = {&a...};
+    (void)hipLaunchKernel(k.fn, grid, dim3(k.threads), args, lds, s);
 }
 
 // prof_ev (optional): [max_iter][ISV_PROF_FAMILIES][2] events recorded around the three dominant
@@ -424,10 +439,10 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     // st2 / fj[4]: side stream + fork/join events: the IMU and prior factor kernels are latency-bound and
     // independent of the reprojection pipeline, so they run beside it and are joined before their consumers
 #define PROF(slot, fam, which) do { if (prof_ev) (void)hipEventRecord(prof_ev[((slot) * ISV_PROF_FAMILIES + (fam)) * 2 + (which)], st); } while (0)
+    const SolverKernel *K = hc.kern;
     const size_t NI = (size_t)d.B * (d.N - 1);
     const size_t lds_proj = 4 * proj_lds_doubles_per_wave(d.N, 0) * sizeof(double), lds_proj1 = 4 * proj_lds_doubles_per_wave(d.N, 1) * sizeof(double);
     if (hc.one_stream) st2 = st;            // diagnostics: serialise everything on one stream (per-kernel timelines)
-    const size_t lds_bs = build_solve_lds_bytes(d.N, false);
     d.ctl_stage_lm = (6 * (size_t)d.lg_lcap * sizeof(double) <= ISV_CTL_STAGE_MAX_BYTES) ? 1 : 0;
     // the priors' J^T J record is staged in k_dogleg's LDS while that keeps the batch in one resident round (else: read from global)
     d.dg_stage_ph = 1;
@@ -444,34 +459,45 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     const bool control_in_wg = d.lds_T && ((size_t)d.Ftot <= (size_t)4096 * d.B || d.est_ex);
     const bool fuse_control = control_in_wg && !hc.split_control && (size_t)d.B <= res_dogleg_ctl;
     const int n_cus = hc.n_cus;
+    // Small-batch handles (hc.chain_split: every workgroup of every kernel finds a CU of its own) run the whole iteration on ONE
+    // stream: an event record costs the critical stream ~7 us and a wait that really blocks ~13 us on this GPU (measured, rocprofv3
+    // kernel trace of one window), more than the kernels they would overlap.  Instead, independent work shares a LAUNCH:
+    // k_front = {IMU factors | prior factors} of every window, k_lin_gram_chain = {k_lin_gram | chain half of the split solve}.
+    const bool cs = hc.chain_split;
+    // (what the visual part of this upload will run, needed here already: k_lin_gram_chain or not)
+    const bool fused = d.lds_T && d.fused_visual;
+    d.sw_global = (d.sw_part && hc.sw_global_ok && (d.B > 256 || hc.debug_sw_global)) ? 1 : 0;     // more than one workgroup per CU: trade LDS for occupancy
+    const int lgw = (fused && d.B <= n_cus && !hc.lg_batch_waves && lin_gram_lds_bytes(d.Nr, !d.sw_global, d.est_ex != 0, LG_WAVES_SMALL, d.lg_lcap) <= ISV_LDS_PER_CU) ? LG_WAVES_SMALL : LG_WAVES;
+    // k_lin_gram_chain takes the chain half; an upload it does not take (windows beyond the fused kernel's limits: BASELINE config 5's
+    // 30 000 factors) runs the chain half (~75 us at 20 frames) on the side stream beside the linearisation and the split elimination --
+    // worth its fork / join events there (on the solve stream behind them it made the one-launch solve's 142 us into 75 + 75)
+    const bool lg_chain = cs && fused && lgw == LG_WAVES_SMALL;
+    // a SMALL batch with LONG windows: one window's elimination over many CUs (k_schur_split + k_schur_fold, isv_sweep.hip)
+    // WHETHER a window's downdates are split is decided by the HANDLE (its max_batch and max_landmarks: ADVICE r4 -- with the groups
+    // counted from the longest window of the upload, a 320-landmark window was split alone and unsplit beside a 2048-landmark one);
+    // into how many groups, by the window (schur_split_groups).  An upload without a window of ISV_SPLIT_MIN_PASSES passes skips
+    // the split launch: its windows are one group each, the unsplit sums.
+    const int Pmax = (d.lg_lcap + 63) / 64, PmaxH = (d.max_lm + 63) / 64, GrMax = PmaxH < d.split_cap ? PmaxH : d.split_cap;
+    const bool split = d.lds_T && d.r1_part && !hc.no_split && Pmax >= ISV_SPLIT_MIN_PASSES && d.split_cap >= 2;
+    // the rank-1 downdates inside k_lin_gram_chain (handles that do not split the elimination)
+    const bool r1_in_lg = lg_chain && K[KR_LIN_GRAM_CHAIN_R1].fn && !split;
+    // the landmark back-substitution on its own workgroups (k_backsub_split) pays for LONG windows only: per landmark it is the same
+    // routine as k_dogleg's first phase (same bits), which takes ~2.5 us for 300 landmarks against 6-8 us for the extra launch
+    const bool bsub_split = split && d.lg_lcap > 1024;
+    d.bs_split = bsub_split ? 1 : 0;
+    // the pose half of the split solve + k_dogleg<true> (dogleg and step control) in one launch: same routines, same bits
+    // (+ the 2 KB of static reduction space)
+    const size_t lds_pd = K[KR_POSE].lds > lds_dgc ? K[KR_POSE].lds : lds_dgc;
+    const bool pose_dogleg = K[KR_POSE_DOGLEG].fn && fuse_control && !bsub_split && lds_pd + 2304 <= ISV_LDS_PER_CU;
     hipLaunchKernelGGL(k_init_state, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
     for (int slot = 0; slot < d.max_iter; slot++) {
         // linearise where needed (k_*_linearize skip windows whose need_linearize == 0 via the tile/window flags)
-        const bool generic_n = hc.generic_n;             // (A/B / test hook: the run-time-N instantiations for every N)
-        // Small-batch handles (hc.chain_split: every workgroup of every kernel finds a CU of its own) run the whole iteration on ONE
-        // stream: an event record costs the critical stream ~7 us and a wait that really blocks ~13 us on this GPU (measured, rocprofv3
-        // kernel trace of one window), more than the kernels they would overlap.  Instead, independent work shares a LAUNCH:
-        // k_front = {IMU factors | prior factors} of every window, k_lin_gram_chain = {k_lin_gram | chain half of the split solve}.
-        const bool cs = d.lds_T && hc.chain_split;
-        bool chain_done = false, rank1_done = false, dogleg_done = false;
-        // (what the visual part of this upload will run, needed here already: k_lin_gram_chain or not)
-        const bool fused = d.lds_T && d.fused_visual;
-        d.sw_global = (d.sw_part && hc.sw_global_ok && (d.B > 256 || hc.debug_sw_global)) ? 1 : 0;     // more than one workgroup per CU: trade LDS for occupancy
-        const int lgw = (fused && d.B <= n_cus && !hc.lg_batch_waves && lin_gram_lds_bytes(d.Nr, !d.sw_global, d.est_ex != 0, LG_WAVES_SMALL, d.lg_lcap) <= ISV_LDS_PER_CU) ? LG_WAVES_SMALL : LG_WAVES;
-        bool chain_on_side = false;
         if (cs) {
-            hipLaunchKernelGGL(k_front, dim3(d.B, 2), dim3(512), front_lds_bytes(d.N, d.n_prior_slots), st, d);
-            if (!(fused && lgw == LG_WAVES_SMALL)) {
-                // an upload k_lin_gram_chain does not take (windows beyond the fused kernel's limits: BASELINE config 5's 30 000 factors):
-                // the chain half (~75 us at 20 frames) on the side stream beside the linearisation and the split elimination -- worth its
-                // fork / join events here (on the solve stream behind them it made the one-launch solve's 142 us into 75 + 75)
+            launch(K[KR_FRONT], dim3(d.B, 2), K[KR_FRONT].lds, st, d);
+            if (!lg_chain) {
                 HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
-                const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz);
-                if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_build_solve_sb<false, 11, 1>), dim3(d.B), dim3(512), lds_sb, st2, d);
-                else if (d.N <= 11) hipLaunchKernelGGL((k_build_solve_sb<false, 0, 1>), dim3(d.B), dim3(512), lds_sb, st2, d);
-                else hipLaunchKernelGGL((k_build_solve_sb<true, 0, 1>), dim3(d.B), dim3(512), lds_sb, st2, d);
+                launch(K[KR_CHAIN], dim3(d.B), K[KR_CHAIN].lds, st2, d);
                 HCHK(hipEventRecord(fj[1], st2));
-                chain_on_side = true; chain_done = true;
             }
         } else {
             HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
@@ -482,157 +508,64 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
             hipLaunchKernelGGL(k_prior_linearize<true>, dim3(d.B), dim3(64), prior_lds_bytes(d.n_prior_slots), st2, d, d.pose, d.sb, d.prior_cost, 1);
             HCHK(hipEventRecord(fj[1], st2));
         }
-        // a SMALL batch with LONG windows: one window's elimination over many CUs (k_schur_split + k_schur_fold, isv_sweep.hip)
-        // WHETHER a window's downdates are split is decided by the HANDLE (its max_batch and max_landmarks: ADVICE r4 -- with the groups
-        // counted from the longest window of the upload, a 320-landmark window was split alone and unsplit beside a 2048-landmark one);
-        // into how many groups, by the window (schur_split_groups).  An upload without a window of ISV_SPLIT_MIN_PASSES passes skips
-        // the split launch: its windows are one group each, the unsplit sums.
-        const int Pmax = (d.lg_lcap + 63) / 64, PmaxH = (d.max_lm + 63) / 64, GrMax = PmaxH < d.split_cap ? PmaxH : d.split_cap;
-        const bool split = d.lds_T && d.r1_part && !hc.no_split && Pmax >= ISV_SPLIT_MIN_PASSES && d.split_cap >= 2;
-        // the landmark back-substitution on its own workgroups (k_backsub_split) pays for LONG windows only: per landmark it is the same
-        // routine as k_dogleg's first phase (same bits), which takes ~2.5 us for 300 landmarks against 6-8 us for the extra launch
-        const bool bsub_split = split && d.lg_lcap > 1024;
-        d.bs_split = bsub_split ? 1 : 0;
         PROF(slot, 0, 0);
         if (fused) {
             // linearisation fused with the Gram products: no Jacobian strip goes to HBM (isv_visual.hip)
             // (eight wavefronts per window while the batch leaves every window a CU of its own: 41 -> 27 us per launch for one window)
-            const bool ex = d.est_ex != 0;
-            const size_t lds_lg = lin_gram_lds_bytes(d.Nr, !d.sw_global, ex, lgw, d.lg_lcap);
-            if (cs && lgw == LG_WAVES_SMALL) {
-                const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz), lds_r1c = (64 * (d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
-                size_t both = lds_lg > lds_sb ? lds_lg : lds_sb;
-                const dim3 g2(d.B, 2);
-                // the rank-1 downdates in the same workgroup (handles that do not split the elimination; the shapes instantiated for it)
-                const int nt = d.wd_ld / 16;
-                const bool r1_here = !split && !ex && !generic_n && d.N > 11 && nt == 7 && lds_r1c <= ISV_LDS_PER_CU;
-                if (r1_here && both < lds_r1c) both = lds_r1c;
-                if (ex) { if (d.N <= 11) hipLaunchKernelGGL((k_lin_gram_chain<true, false, 0, 0>), g2, dim3(512), both, st, d); else hipLaunchKernelGGL((k_lin_gram_chain<true, true, 0, 0>), g2, dim3(512), both, st, d); }
-                else if (r1_here) hipLaunchKernelGGL((k_lin_gram_chain<false, true, 0, 7>), g2, dim3(512), both, st, d);
-                else if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_lin_gram_chain<false, false, 11, 0>), g2, dim3(512), both, st, d);
-                else if (d.N <= 11) hipLaunchKernelGGL((k_lin_gram_chain<false, false, 0, 0>), g2, dim3(512), both, st, d);
-                else hipLaunchKernelGGL((k_lin_gram_chain<false, true, 0, 0>), g2, dim3(512), both, st, d);
-                chain_done = true; rank1_done = r1_here;
-            } else if (lgw == LG_WAVES_SMALL) {
-                if (ex) hipLaunchKernelGGL((k_lin_gram<true, LG_WAVES_SMALL>), dim3(d.B), dim3(64 * LG_WAVES_SMALL), lds_lg, st, d);
-                else hipLaunchKernelGGL((k_lin_gram<false, LG_WAVES_SMALL>), dim3(d.B), dim3(64 * LG_WAVES_SMALL), lds_lg, st, d);
-            } else if (ex) hipLaunchKernelGGL((k_lin_gram<true, LG_WAVES>), dim3(d.B), dim3(64 * LG_WAVES), lds_lg, st, d);
-            else hipLaunchKernelGGL((k_lin_gram<false, LG_WAVES>), dim3(d.B), dim3(64 * LG_WAVES), lds_lg, st, d);
-            counts[0]++; counts[4] = 1;
-        } else if (d.n_tiles > 0) { hipLaunchKernelGGL(k_proj_linearize<0>, dim3((d.n_tiles + 3) / 4), dim3(256), lds_proj, st, d, d.pose, d.lam, d.fcost, 1); counts[0]++; }
+            const size_t lds_lg = lin_gram_lds_bytes(d.Nr, !d.sw_global, d.est_ex != 0, lgw, d.lg_lcap);
+            if (lg_chain) {
+                size_t both = lds_lg > K[KR_CHAIN].lds ? lds_lg : K[KR_CHAIN].lds;
+                if (r1_in_lg && both < K[KR_RANK1].lds) both = K[KR_RANK1].lds;
+                launch(K[r1_in_lg ? KR_LIN_GRAM_CHAIN_R1 : KR_LIN_GRAM_CHAIN], dim3(d.B, 2), both, st, d);
+            } else launch(K[lgw == LG_WAVES_SMALL ? KR_LIN_GRAM_SMALL : KR_LIN_GRAM], dim3(d.B), lds_lg, st, d);
+            counts[ISV_CNT_LINEARIZE]++; counts[ISV_CNT_FUSED_VISUAL] = 1;
+        } else if (d.n_tiles > 0) { hipLaunchKernelGGL(k_proj_linearize<0>, dim3((d.n_tiles + 3) / 4), dim3(256), lds_proj, st, d, d.pose, d.lam, d.fcost, 1); counts[ISV_CNT_LINEARIZE]++; }
         PROF(slot, 0, 1);
         if (split) {
             int Gs = 0;
             if (!fused) { Gs = n_cus / d.B - GrMax; if (Gs > 16) Gs = 16; if (Gs < 1) Gs = 1; }
-            const int nt = d.wd_ld / 16;
-            const size_t n_pairs = (size_t)d.N * (d.N - 1) / 2;
-            size_t lds_sp = (64 * (d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
-            const size_t lds_r1s = lds_sp;
-            if (lds_sp < (2 * n_pairs + 2) * sizeof(int)) lds_sp = (2 * n_pairs + 2) * sizeof(int);
             const dim3 grid(d.B, Gs + GrMax);
             PROF(slot, 1, 0);
-            if (Gs == 0) switch (nt) {          // the downdates alone: the lean kernel (two workgroups per CU)
-            case 1: hipLaunchKernelGGL((k_rank1_split<1, 1>), grid, dim3(64 * 1), lds_r1s, st, d, GrMax); break;
-            case 2: hipLaunchKernelGGL((k_rank1_split<2, 1>), grid, dim3(64 * 3), lds_r1s, st, d, GrMax); break;
-            case 3: hipLaunchKernelGGL((k_rank1_split<3, 1>), grid, dim3(64 * 6), lds_r1s, st, d, GrMax); break;
-            case 4: hipLaunchKernelGGL((k_rank1_split<4, 1>), grid, dim3(64 * 10), lds_r1s, st, d, GrMax); break;
-            case 5: hipLaunchKernelGGL((k_rank1_split<5, 1>), grid, dim3(64 * 15), lds_r1s, st, d, GrMax); break;
-            case 6: hipLaunchKernelGGL((k_rank1_split<6, 2>), grid, dim3(64 * 11), lds_r1s, st, d, GrMax); break;
-            case 7: hipLaunchKernelGGL((k_rank1_split<7, 2>), grid, dim3(64 * 14), lds_r1s, st, d, GrMax); break;
-            default: hipLaunchKernelGGL((k_rank1_split<8, 3>), grid, dim3(64 * 12), lds_r1s, st, d, GrMax); break;
-            }
-            else switch (nt) {
-            case 1: hipLaunchKernelGGL((k_schur_split<1, 1>), grid, dim3(64 * 1), lds_sp, st, d, Gs, GrMax); break;
-            case 2: hipLaunchKernelGGL((k_schur_split<2, 1>), grid, dim3(64 * 3), lds_sp, st, d, Gs, GrMax); break;
-            case 3: hipLaunchKernelGGL((k_schur_split<3, 1>), grid, dim3(64 * 6), lds_sp, st, d, Gs, GrMax); break;
-            case 4: hipLaunchKernelGGL((k_schur_split<4, 1>), grid, dim3(64 * 10), lds_sp, st, d, Gs, GrMax); break;
-            case 5: hipLaunchKernelGGL((k_schur_split<5, 1>), grid, dim3(64 * 15), lds_sp, st, d, Gs, GrMax); break;
-            case 6: hipLaunchKernelGGL((k_schur_split<6, 2>), grid, dim3(64 * 11), lds_sp, st, d, Gs, GrMax); break;
-            case 7: hipLaunchKernelGGL((k_schur_split<7, 2>), grid, dim3(64 * 14), lds_sp, st, d, Gs, GrMax); break;
-            default: hipLaunchKernelGGL((k_schur_split<8, 3>), grid, dim3(64 * 12), lds_sp, st, d, Gs, GrMax); break;
-            }
+            if (Gs == 0) launch(K[KR_RANK1_SPLIT], grid, K[KR_RANK1_SPLIT].lds, st, d, GrMax);          // the downdates alone: the lean kernel (two workgroups per CU)
+            else launch(K[KR_SCHUR_SPLIT], grid, K[KR_SCHUR_SPLIT].lds, st, d, Gs, GrMax);
             PROF(slot, 1, 1);
             PROF(slot, 2, 0);
+            const int nt = d.wd_ld / 16;
             hipLaunchKernelGGL(k_schur_fold, dim3(d.B, nt * (nt + 1) / 2), dim3(256), 0, st, d, GrMax, nt, Gs > 0 ? 1 : 0);      // one accumulator-tile entry per thread
             PROF(slot, 2, 1);
-            counts[2]++; counts[7] = GrMax;
+            counts[ISV_CNT_ELIM]++; counts[ISV_CNT_SPLIT_GROUPS] = GrMax;
         } else if (d.lds_T) {
             // landmark elimination: Gram products of the pose Jacobians, then the rank-1 downdates (both FP64 MFMA)
             PROF(slot, 1, 0);
             if (!fused) {
                 const size_t n_pairs = (size_t)d.N * (d.N - 1) / 2;
-                hipLaunchKernelGGL(k_sweep_mfma, dim3(d.B), dim3(64 * ISV_SWEEP_WAVES), ((d.sw_global ? 0 : n_pairs * 84) + (n_pairs + 2) / 2 + 1) * sizeof(double), st, d);
+                launch(K[KR_SWEEP], dim3(d.B), ((d.sw_global ? 0 : n_pairs * 84) + (n_pairs + 2) / 2 + 1) * sizeof(double), st, d);
             }
-            counts[2]++;
+            counts[ISV_CNT_ELIM]++;
             PROF(slot, 1, 1);
-            const int nt = d.wd_ld / 16;
             // one workgroup per window: nt(nt+1)/2 tile wavefronts, w vectors expanded to panel rows in LDS
-            const size_t lds_r1 = (64 * (d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
             PROF(slot, 2, 0);
-            if (!rank1_done) switch (nt) {
-            case 1: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<1, 1, 64, 1, true>), dim3(d.B), dim3(64 * 1), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<1, 1, 64, 1, false>), dim3(d.B), dim3(64 * 1), lds_r1, st, d); break;
-            case 2: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<2, 1, 64, 1, true>), dim3(d.B), dim3(64 * 3), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<2, 1, 64, 1, false>), dim3(d.B), dim3(64 * 3), lds_r1, st, d); break;
-            case 3: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<3, 1, 64, 1, true>), dim3(d.B), dim3(64 * 6), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<3, 1, 64, 1, false>), dim3(d.B), dim3(64 * 6), lds_r1, st, d); break;
-            case 4: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<4, 1, 64, 1, true>), dim3(d.B), dim3(64 * 10), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<4, 1, 64, 1, false>), dim3(d.B), dim3(64 * 10), lds_r1, st, d); break;
-            case 5: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<5, 1, 64, 1, true>), dim3(d.B), dim3(64 * 15), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<5, 1, 64, 1, false>), dim3(d.B), dim3(64 * 15), lds_r1, st, d); break;
-            case 6: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<6, 2, 64, 1, true>), dim3(d.B), dim3(64 * 11), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<6, 2, 64, 1, false>), dim3(d.B), dim3(64 * 11), lds_r1, st, d); break;
-            case 7: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<7, 2, 64, 1, true>), dim3(d.B), dim3(64 * 14), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<7, 2, 64, 1, false>), dim3(d.B), dim3(64 * 14), lds_r1, st, d); break;
-            default: if (d.est_ex) hipLaunchKernelGGL((k_rank1_mfma<8, 3, 64, 1, true>), dim3(d.B), dim3(64 * 12), lds_r1, st, d); else hipLaunchKernelGGL((k_rank1_mfma<8, 3, 64, 1, false>), dim3(d.B), dim3(64 * 12), lds_r1, st, d); break;
-            }
+            if (!r1_in_lg) launch(K[KR_RANK1], dim3(d.B), K[KR_RANK1].lds, st, d);
             PROF(slot, 2, 1);
         }
-        if (!cs || chain_on_side) HCHK(hipStreamWaitEvent(st, fj[1], 0));
-        if (cs && !chain_done) {                          // (an upload k_lin_gram_chain does not take: the chain half alone; same bits)
-            const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz);
-            if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_build_solve_sb<false, 11, 1>), dim3(d.B), dim3(512), lds_sb, st, d);
-            else if (d.N <= 11) hipLaunchKernelGGL((k_build_solve_sb<false, 0, 1>), dim3(d.B), dim3(512), lds_sb, st, d);
-            else hipLaunchKernelGGL((k_build_solve_sb<true, 0, 1>), dim3(d.B), dim3(512), lds_sb, st, d);
-        }
+        if (!lg_chain) HCHK(hipStreamWaitEvent(st, fj[1], 0));
         if (!d.lds_T) hipLaunchKernelGGL(k_cost_reduce, dim3(d.B), dim3(256), 0, st, d, d.fcost, d.imu_cost, d.prior_cost, d.cost, 1);   // (k_build_solve_sb sums the cost itself)
         PROF(slot, 3, 0);
-        // (the window length as a compile-time constant for the benchmark's 11 frames: isv_build_solve_sb.hip)
-        if (d.lds_T && hc.solve_st) {
-            counts[6] = 1;
-            const size_t lds_st = build_solve_st_bytes(d.N, d.prior_H_sz);
-            if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_build_solve_st<false, 11>), dim3(d.B), dim3(256), lds_st, st, d);
-            else if (d.N <= 11) hipLaunchKernelGGL((k_build_solve_st<false, 0>), dim3(d.B), dim3(256), lds_st, st, d);
-            // (the reference's ALL_BUF_SIZE as a compile-time constant: 404 -> 357 us per launch, 1024 windows 10.27 -> 9.87 ms.  The same for
-            //  k_build_solve_sb<true, 18> spills 62 registers and is SLOWER for the single window it serves: 2.54 against 2.48 ms; not instantiated)
-            else if (d.N == 18 && !generic_n) hipLaunchKernelGGL((k_build_solve_st<true, 18>), dim3(d.B), dim3(512), lds_st, st, d);     // (the reference's ALL_BUF_SIZE)
-            else hipLaunchKernelGGL((k_build_solve_st<true, 0>), dim3(d.B), dim3(512), lds_st, st, d);       // (long windows: eight wavefronts, two windows per CU)
-        } else if (d.lds_T && hc.chain_split && fuse_control && !bsub_split && !hc.no_pose_dogleg && d.N <= 11 &&      // (measured: 128 windows of 11 frames 1.92 -> 1.86 ms; the 18-frame
-                   // form LOSES -- 117 us against 70 + 37 for the two launches, rocprofv3 -- and is not used)
-                   (build_solve_sb_bytes(d.N, d.prior_H_sz) > lds_dgc ? build_solve_sb_bytes(d.N, d.prior_H_sz) : lds_dgc) + 2304 <= ISV_LDS_PER_CU) {       // (+ the 2 KB of static reduction space)
-            // the pose half of the split solve + k_dogleg<true> (dogleg and step control) in one launch: same routines, same bits
-            const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz), lds_pd = lds_sb > lds_dgc ? lds_sb : lds_dgc;
-            if (d.est_ex) { if (d.N <= 11) hipLaunchKernelGGL((k_pose_dogleg<false, 0, true>), dim3(d.B), dim3(512), lds_pd, st, d); else hipLaunchKernelGGL((k_pose_dogleg<true, 0, true>), dim3(d.B), dim3(512), lds_pd, st, d); }
-            else if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_pose_dogleg<false, 11, false>), dim3(d.B), dim3(512), lds_pd, st, d);
-            else if (d.N <= 11) hipLaunchKernelGGL((k_pose_dogleg<false, 0, false>), dim3(d.B), dim3(512), lds_pd, st, d);
-            else hipLaunchKernelGGL((k_pose_dogleg<true, 0, false>), dim3(d.B), dim3(512), lds_pd, st, d);
-            dogleg_done = true; counts[5] = 1;
-        } else if (d.lds_T && hc.chain_split) {           // the pose half of the split solve (the chain half ran beside k_lin_gram)
-            const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz);
-            if (d.N == 11 && !generic_n) hipLaunchKernelGGL((k_build_solve_sb<false, 11, 2>), dim3(d.B), dim3(512), lds_sb, st, d);
-            else if (d.N <= 11) hipLaunchKernelGGL((k_build_solve_sb<false, 0, 2>), dim3(d.B), dim3(512), lds_sb, st, d);
-            else hipLaunchKernelGGL((k_build_solve_sb<true, 0, 2>), dim3(d.B), dim3(512), lds_sb, st, d);
-        } else if (d.lds_T && generic_n) {
-            if (d.N <= 11) hipLaunchKernelGGL((k_build_solve_sb<false, 0, 0>), dim3(d.B), dim3(512), build_solve_sb_bytes(d.N, d.prior_H_sz), st, d);
-            else hipLaunchKernelGGL((k_build_solve_sb<true, 0, 0>), dim3(d.B), dim3(512), build_solve_sb_bytes(d.N, d.prior_H_sz), st, d);
-        } else if (d.lds_T && d.N == 11) hipLaunchKernelGGL((k_build_solve_sb<false, 11, 0>), dim3(d.B), dim3(512), build_solve_sb_bytes(d.N, d.prior_H_sz), st, d);
-        else if (d.lds_T && d.N < 11) hipLaunchKernelGGL((k_build_solve_sb<false, 0, 0>), dim3(d.B), dim3(512), build_solve_sb_bytes(d.N, d.prior_H_sz), st, d);
-        else if (d.lds_T) hipLaunchKernelGGL((k_build_solve_sb<true, 0, 0>), dim3(d.B), dim3(512), build_solve_sb_bytes(d.N, d.prior_H_sz), st, d);
-        else hipLaunchKernelGGL(k_build_solve<false>, dim3(d.B), dim3(512), lds_bs, st, d);
-        counts[1]++;
+        // the whole reduced solve, or on chain-split handles its pose half (the chain half ran beside k_lin_gram), with the dogleg
+        // and the step control when they fit one launch
+        if (pose_dogleg) { launch(K[KR_POSE_DOGLEG], dim3(d.B), lds_pd, st, d); counts[ISV_CNT_FUSED_CONTROL] = 1; }
+        else if (cs) launch(K[KR_POSE], dim3(d.B), K[KR_POSE].lds, st, d);
+        else launch(K[KR_SOLVE], dim3(d.B), K[KR_SOLVE].lds, st, d);
+        if (hc.solve_st) counts[ISV_CNT_SOLVE_ST] = 1;
+        counts[ISV_CNT_SOLVE]++;
         PROF(slot, 3, 1);
         PROF(slot, 4, 0);
         if (bsub_split) hipLaunchKernelGGL(k_backsub_split, dim3(d.B, (d.lg_lcap + 127) / 128), dim3(128), 2 * (size_t)d.np * sizeof(double), st, d);
-        if (dogleg_done) {
+        if (pose_dogleg) {
         } else if (fuse_control) {
-            if (d.est_ex) hipLaunchKernelGGL((k_dogleg<true, true>), dim3(d.B), dim3(256), lds_dgc, st, d);
-            else hipLaunchKernelGGL((k_dogleg<true, false>), dim3(d.B), dim3(256), lds_dgc, st, d);
-            counts[5] = 1;
-        } else if (d.est_ex) hipLaunchKernelGGL((k_dogleg<false, true>), dim3(d.B), dim3(256), lds_dg, st, d);
-        else hipLaunchKernelGGL((k_dogleg<false, false>), dim3(d.B), dim3(256), lds_dg, st, d);
+            launch(K[KR_DOGLEG_CONTROL], dim3(d.B), lds_dgc, st, d);
+            counts[ISV_CNT_FUSED_CONTROL] = 1;
+        } else launch(K[KR_DOGLEG], dim3(d.B), lds_dg, st, d);
         PROF(slot, 4, 1);
         if (!d.lds_T) {                    // (the LDS path evaluates these inside k_dogleg)
             HCHK(hipEventRecord(fj[2], st)); HCHK(hipStreamWaitEvent(st2, fj[2], 0));
@@ -645,10 +578,7 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
         // so large that one workgroup per window would serialise it (config 5: 30 000 factors in one window)
         PROF(slot, 5, 0);
         if (fuse_control) {
-        } else if (control_in_wg) {
-            if (d.est_ex) hipLaunchKernelGGL((k_step_control<true, true>), dim3(d.B), dim3(256), lds_sc, st, d);
-            else hipLaunchKernelGGL((k_step_control<true, false>), dim3(d.B), dim3(256), lds_sc, st, d);
-        }
+        } else if (control_in_wg) launch(K[KR_STEP_CONTROL], dim3(d.B), lds_sc, st, d);
         else {
             if (d.n_tiles > 0) hipLaunchKernelGGL(k_proj_linearize<1>, dim3((d.n_tiles + 3) / 4), dim3(256), lds_proj1, st, d, d.cpose, d.clam, d.fcost_c, 2);
             if (!d.lds_T) HCHK(hipStreamWaitEvent(st, fj[3], 0));

@@ -137,6 +137,7 @@ __global__ __launch_bounds__(64 * ((NT * (NT + 1) / 2 + TPW - 1) / TPW), MINW) v
 // NT = 5 (the benchmark's 11 frames): 15 wavefronts per workgroup, and two workgroups share a CU only at eight wavefronts
 // per SIMD, i.e. <= 64 VGPRs -- the launch bounds alone let the compiler settle at 66-70 (occupancy 7: ONE workgroup per CU)
 template <> __global__ __launch_bounds__(960) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_rank1_mfma<5, 1, 64, 1, false>(DevBatch d) { rank1_body<5, 1, 64, 1, false>(d); }
+// (every form the solver's per-handle kernel table can name: isv_solver_alloc)
 template __global__ void k_rank1_mfma<1, 1, 64, 1, false>(DevBatch);
 template __global__ void k_rank1_mfma<1, 1, 64, 1, true>(DevBatch);
 template __global__ void k_rank1_mfma<2, 1, 64, 1, false>(DevBatch);
@@ -145,6 +146,7 @@ template __global__ void k_rank1_mfma<3, 1, 64, 1, false>(DevBatch);
 template __global__ void k_rank1_mfma<3, 1, 64, 1, true>(DevBatch);
 template __global__ void k_rank1_mfma<4, 1, 64, 1, false>(DevBatch);
 template __global__ void k_rank1_mfma<4, 1, 64, 1, true>(DevBatch);
+// k_rank1_mfma<5, 1, 64, 1, false>: the explicit specialisation above (a definition of its own)
 template __global__ void k_rank1_mfma<5, 1, 64, 1, true>(DevBatch);
 template __global__ void k_rank1_mfma<6, 2, 64, 1, false>(DevBatch);
 template __global__ void k_rank1_mfma<6, 2, 64, 1, true>(DevBatch);
@@ -281,6 +283,7 @@ template __global__ void k_rank1_split<1, 1>(DevBatch, int);
 template __global__ void k_rank1_split<2, 1>(DevBatch, int);
 template __global__ void k_rank1_split<3, 1>(DevBatch, int);
 template __global__ void k_rank1_split<4, 1>(DevBatch, int);
+// k_rank1_split<5, 1>: the explicit specialisation above
 template __global__ void k_rank1_split<6, 2>(DevBatch, int);
 template __global__ void k_rank1_split<7, 2>(DevBatch, int);
 template __global__ void k_rank1_split<8, 3>(DevBatch, int);
