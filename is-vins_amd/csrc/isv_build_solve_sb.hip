@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include "isv_kernels.h"
 #include "isv_device_math.h"
+#include "isv_chain.h"
 #include "isv_lin_gram.h"
 #include "isv_rank1.h"
 #include "isv_dogleg.h"
@@ -41,69 +42,11 @@ __host__ __device__ inline int sb_nred(int N, int prior_H_sz) {   // doubles in 
     if (30 * N > m) m = 30 * N;
     return (m + 1) & ~1;
 }
-// a fresh, opaque copy of the thread id per phase: index arithmetic is then recomputed where it is used instead of being
-// shared across phases by CSE -- the shared values live through the whole kernel and spill under the 128-VGPR cap, and
-// every reload is a scratch (global memory) round trip on the serial path
-#define PHASE_IDS() int t = t_outer; asm volatile("" : "+v"(t)); const int lane = t & 63; (void)lane
 #define RCH 32                     // landmarks per staged chunk of the retry correction
 
-DEV int sblk(int I, int J, int N) { return (J * N - J * (J - 1) / 2 + (I - J)) * 36; }   // I >= J
 // the non-visual pose blocks are block-tridiagonal (IMU factors and relative-pose priors couple neighbours, the other priors one pose):
 // the chain kernel of the split solve (MODE 1) keeps them as N diagonal blocks followed by N - 1 sub-diagonal ones
 DEV int sbt(int I, int J, int N) { return (I == J ? I : N + J) * 36; }
-DEV int pairidx2(int a, int b) { return a * (a + 1) / 2 + b; }      // a >= b
-DEV int nlo(int i, int M) { return i > M ? i - 1 : 0; }
-DEV int nhi(int i, int M, int N) { return i < M ? i + 1 : N - 1; }
-DEV int npar(int i, int M) { return i < M ? i + 1 : (i > M ? i - 1 : -1); }
-
-DEV double readlane_d2(double v, int lane) {
-    union { double d; int i[2]; } u; u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], lane);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
-    return u.d;
-}
-DEV double rsqrt_nr2(double x) {   // 1/sqrt(x) to ~1 ulp: hardware estimate + two Newton steps
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-// wave-level ordering of LDS traffic (LDS executes one wavefront's accesses in issue order)
-#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
-// Factor the BS x BS SPD block at A (row-major, leading dimension BS, lower part valid) in registers and
-// overwrite it with the INVERSE of its Cholesky factor (lower, upper part zeroed).  One wavefront.
-template <int BS>
-DEV bool chol_inv_block(double *A, int lane) {
-    double row[BS], dinv[BS], x[BS];
-#pragma unroll
-    for (int k = 0; k < BS; k++) row[k] = (lane < BS) ? A[lane * BS + k] : 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < BS; j++) {
-        double s = row[j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= row[k] * readlane_d2(row[k], j);
-        const double sj = readlane_d2(s, j);               // pivot
-        if (!(sj > 0.0)) bad = true;
-        dinv[j] = rsqrt_nr2(sj);                            // 1 / L_jj (wave-uniform)
-        row[j] = (lane == j) ? sj * dinv[j] : s * dinv[j];
-    }
-#pragma unroll
-    for (int i = 0; i < BS; i++) {                          // lane c solves L x = e_c
-        double s = (lane == i) ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= readlane_d2(row[k], i) * x[k];
-        x[i] = s * dinv[i];
-    }
-    WSYNC();
-    if (lane < BS) {
-#pragma unroll
-        for (int k = 0; k < BS; k++) A[k * BS + lane] = x[k];   // x[k] = Linv[k][lane], zero for k < lane
-    }
-    WSYNC();
-    return bad;
-}
 
 // BIG = false: N <= 11, two workgroups per CU (<= 128 VGPRs), register prefetch of the assembly, chain back-
 //               substitution with all nodes of a chain in one register;
@@ -124,10 +67,7 @@ DEV bool chol_inv_block(double *A, int lane) {
 // The split sums the same products in a different order than MODE 0 (the row scaling is applied after the chain instead of before): results agree to
 // rounding; which one a handle runs is decided by its max_batch (SolverHost::chain_split), never by the uploaded batch.
 __host__ __device__ inline size_t sb_cs_doubles(int N) {
-    const int M = N / 2;
-    size_t ytot = 0;
-    for (int i = 0; i < N; i++) ytot += (size_t)((i < M ? i + 1 : N - 1) - (i > M ? i - 1 : 0) + 1) * 54;
-    return (2 * (size_t)N - 1) * 36 + (size_t)N * (N + 1) / 2 * 36 + 162 * (size_t)N + ytot + 3 * 15 * (size_t)N + 6 * (size_t)N + 8;
+    return (2 * (size_t)N - 1) * 36 + (size_t)N * (N + 1) / 2 * 36 + 162 * (size_t)N + chain_fill_doubles<size_t>(N) + 3 * 15 * (size_t)N + 6 * (size_t)N + 8;
 }
 template <bool BIG, int NC, int MODE>
 DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
@@ -221,7 +161,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         const bool pre = MODE == 2 && attempt == 0;
         if (pre && CS_sc[1] != 0.0) { mu *= 10.0; attempt++; continue; }
         if (pre) {
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             // ---- (1) vectors: visual diagonal / gradient / reduced rhs + the non-visual parts and the chain's right-hand sides
             double vh = 0, vg = 0, vy = 0, vs = 0, vd = 0, vT0 = 0, vT1 = 0, vT2 = 0, vtY = 0;
             const bool sbrow = t < n && (t % 15) >= 6;
@@ -344,15 +284,15 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
             int ia, ib;
             if (q < 21) {
                 const int r = triAB[2 * q], c = triAB[2 * q + 1];
-                ia = pairidx2(15 + r, 15 + c); ib = pairidx2(r, c);
+                ia = pairidx(15 + r, 15 + c); ib = pairidx(r, c);
             } else if (q < 66) {
                 q -= 21;
                 const int r = triAB[2 * q], c = triAB[2 * q + 1];
-                ia = pairidx2(21 + r, 21 + c); ib = pairidx2(6 + r, 6 + c);
+                ia = pairidx(21 + r, 21 + c); ib = pairidx(6 + r, 6 + c);
             } else {
                 q -= 66;
                 const int r = q / 9, c = q - 9 * r;         // pose row r, speed/bias column c of frame I
-                ia = pairidx2(21 + c, 15 + r); ib = pairidx2(6 + c, r);
+                ia = pairidx(21 + c, 15 + r); ib = pairidx(6 + c, r);
             }
             double v = 0;
             if (hasA) v += HA[ia];
@@ -381,10 +321,10 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
             if (skipL[I]) return 0.0;
             const double *HB = H + (size_t)I * ISV_IMU_H;
             int ib;
-            if (q < 36) { const int r = q / 6, c = q - 6 * r; ib = pairidx2(15 + r, c); }
-            else if (q < 90) { q -= 36; const int r = q / 9, c = q - 9 * r; ib = pairidx2(15 + r, 6 + c); }      // pose_{I+1} x sb_I
-            else if (q < 144) { q -= 90; const int r = q / 9, c = q - 9 * r; ib = pairidx2(21 + c, r); }          // pose_I x sb_{I+1}
-            else { q -= 144; const int r = q / 9, c = q - 9 * r; ib = pairidx2(21 + r, 6 + c); }                  // sb_{I+1} (r) x sb_I (c)
+            if (q < 36) { const int r = q / 6, c = q - 6 * r; ib = pairidx(15 + r, c); }
+            else if (q < 90) { q -= 36; const int r = q / 9, c = q - 9 * r; ib = pairidx(15 + r, 6 + c); }      // pose_{I+1} x sb_I
+            else if (q < 144) { q -= 90; const int r = q / 9, c = q - 9 * r; ib = pairidx(21 + c, r); }          // pose_I x sb_{I+1}
+            else { q -= 144; const int r = q / 9, c = q - 9 * r; ib = pairidx(21 + r, 6 + c); }                  // sb_{I+1} (r) x sb_I (c)
             return HB[ib];
         };
         auto imu_pair_apply = [&](int e, double v) {
@@ -531,7 +471,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         }
         STAMP(2);
         // ---- Jacobi scaling, LM diagonal, Cauchy data -------------------------------------------------
-        { PHASE_IDS();
+        { ISV_PHASE_IDS();
         if (MODE == 1) {
             // the non-visual pose blocks, gradient and diagonal as assembled (unscaled): the pose kernel adds the visual part
             for (int e = t; e < (2 * N - 1) * 36; e += LS) CS_snv[e] = Spp[e];
@@ -553,7 +493,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         __syncthreads();
         }
         {   // qT = u^T T u on the unscaled blocks, then scale in place and add the LM diagonal
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             double accq = 0;
             if (MODE == 1) {
                 // t_Y[pose row] = sum over the speed/bias columns of (unscaled Y) u: the pose kernel adds 2 u_pose . t_Y to u^T T u
@@ -627,7 +567,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         // node i: (1) D_i -> inverse Cholesky factor; (2) rows of [C_i ; Y_i] times L_i^-T;
         //         (3) downdate the parent's diagonal block and pose coupling (not for children of M here:
         //             both chains end in M, those two downdates are applied after the join).
-        { PHASE_IDS();
+        { ISV_PHASE_IDS();
         auto node_rows = [&](int i, bool has_par) {            // step (2), executed by one wavefront
             // the right-hand side rides along as one more row: z_i^T = y_i^T L_i^-T (forward substitution)
             const int nr = nhi(i, M, N) - nlo(i, M) + 1, nrows = (has_par ? 9 : 0) + 6 * nr + 1;
@@ -648,7 +588,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
 #pragma unroll
                 for (int k = 0; k < 9; k++) ptr[k] = o[k];
             }
-            WSYNC();
+            ISV_WSYNC();
         };
         auto node_downdate = [&](int i, int lid, int nl) {     // step (3) with nl lanes, lane id lid
             const int pp = npar(i, M), lo = nlo(i, M), nr = nhi(i, M, N) - lo + 1;
@@ -698,7 +638,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
 #pragma unroll
                 for (int k = 0; k < 9; k++) ptr[k] = o[k];
             }
-            WSYNC();
+            ISV_WSYNC();
         };
         auto crit_downdate = [&](int i) {                      // D_p -= C_i C_i^T, y_p -= C_i z_i
             const int pp = npar(i, M);
@@ -716,7 +656,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 for (int k = 0; k < 9; k++) s += C[r * 9 + k] * y[15 * i + 6 + k];
                 y[15 * pp + 6 + r] -= s;
             }
-            WSYNC();
+            ISV_WSYNC();
         };
         auto y_rows = [&](int i, bool downdate) {              // Y_i L_i^-T, then Y_p -= Y_i C_i^T (C_i already transformed)
             const int pp = npar(i, M), lo = nlo(i, M), nr = nhi(i, M, N) - lo + 1;
@@ -786,7 +726,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         STAMP(4);
         if (!flag[0]) {
             // ---- pose system: Spp -= sum_i Y_i Y_i^T ---------------------------------------------------
-            { PHASE_IDS();
+            { ISV_PHASE_IDS();
             if constexpr (BIG) {
             // (round 3) a thread owns a 3 x 6 half of a 6x6 pose block: per k it reads three values of Y_I and six of Y_J for
             // eighteen products (9 LDS reads per 18 FMAs; one entry per thread needed 2 per FMA, the 2 x 3 sub-blocks of the
@@ -884,7 +824,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         }
         if (MODE == 1) {
             // hand-over to the pose kernel (same workgroup index, after the join of the two streams)
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             if (!flag[0]) {
                 for (int e = t; e < tailsz; e += LS) CS_tail[e] = Dss[e];          // L_i^-1 | C_i' | Y_i'
                 for (int e = t; e < n; e += LS) CS_y[e] = y[e];                    // z_i; pose rows: -sum_i Y_i' z_i
@@ -900,7 +840,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
             // Look-ahead: while wavefronts 1..7 apply the trailing update of step J, wavefront 0 updates the NEXT diagonal block
             // first and factors it, so the factorisation's dependent pivots and one barrier per step leave the critical path.
             // Entry for entry the same sums as a plain right-looking sweep.
-            { PHASE_IDS();
+            { ISV_PHASE_IDS();
             if (wv == 0 && chol_inv_block<6>(Spp + sblk(0, 0, N), lane)) { if (lane == 0) flag[0] = 1; }
             __syncthreads();
             for (int J = 0; J < N; J++) {
@@ -950,7 +890,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 };
                 if (wv == 0) {
                     if (lane < 36) trailing_entry(lane);         // block (J+1, J+1) is the first of the trailing storage
-                    WSYNC();
+                    ISV_WSYNC();
                     if (chol_inv_block<6>(Spp + e0, lane)) { if (lane == 0) flag[0] = 1; }
                 } else {
                     if constexpr (BIG) {
@@ -1028,7 +968,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         // + r), yp1 frames 10.. ; pivot vectors travel by v_readlane, every lane forms its own row's dot
         // product: the N dependent steps need no LDS round trip and no barrier.
         if (wv == 0) {
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             const int q6 = lane / 6, c6 = lane - 6 * q6;
             const int fA = q6, fB = 10 + q6;                    // my frame in yp0 / yp1
             const bool hasPA = q6 < 10 && fA < N, hasPB = q6 < 10 && fB < N;
@@ -1037,14 +977,14 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 const int b = 6 * (J % 10);
                 double v[6];
 #pragma unroll
-                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d2(yp0, b + k) : readlane_d2(yp1, b + k);
+                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d(yp0, b + k) : readlane_d(yp1, b + k);
                 const double *Lc = Spp + sblk(J, J, N) + c6;    // column c6 of L_JJ^-1
                 double x = 0;
 #pragma unroll
                 for (int k = 0; k < 6; k++) x += Lc[k * 6] * v[k];
                 if (J < 10) { if (hasPA && fA == J) yp0 = x; } else { if (hasPB && fB == J) yp1 = x; }
 #pragma unroll
-                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d2(yp0, b + k) : readlane_d2(yp1, b + k);
+                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d(yp0, b + k) : readlane_d(yp1, b + k);
                 if (hasPA && fA < J) {
                     const double *Lb = Spp + sblk(J, fA, N) + c6;
 #pragma unroll
@@ -1061,7 +1001,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         }
         __syncthreads();
         // chain rhs -= Y_i^T x_pose: thread = (speed/bias row, quarter of the pose blocks), folded in fixed order
-        { PHASE_IDS();
+        { ISV_PHASE_IDS();
         for (int tq = t; tq < 36 * N; tq += LS) {
             const int o = tq >> 2, part = tq & 3, i = o / 9, c = o - 9 * i, lo = nlo(i, M), nr = nhi(i, M, N) - lo + 1;
             const double *Yc = Ysb + yo[i] + c;
@@ -1095,10 +1035,10 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 }
                 double x = 0;
 #pragma unroll
-                for (int k = 0; k < 9; k++) x += Dss[i * 81 + k * 9 + cl] * readlane_d2(sv, k);
-                WSYNC();
+                for (int k = 0; k < 9; k++) x += Dss[i * 81 + k * 9 + cl] * readlane_d(sv, k);
+                ISV_WSYNC();
                 if (lane < 9) y[15 * i + 6 + lane] = x;
-                WSYNC();
+                ISV_WSYNC();
             };
             if (wv == 0) node_bwd_lds(M, -1);
             __syncthreads();
@@ -1106,7 +1046,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
             else if (wv == 1) { for (int i = M + 1; i <= N - 1; i++) node_bwd_lds(i, i - 1); }
         } else {
         if (wv < 2) {
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             const int q9 = lane / 9, c9 = lane - 9 * q9;
             const int mynode = wv == 0 ? q9 : M + 1 + q9;
             const bool has = q9 < 7 && (wv == 0 ? mynode <= M : mynode <= N - 1);
@@ -1118,7 +1058,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 double v[9];
                 if (pp >= 0) {
 #pragma unroll
-                    for (int k = 0; k < 9; k++) v[k] = par_in_lds ? y[15 * pp + 6 + k] : readlane_d2(ys, sb_base(pp) + k);
+                    for (int k = 0; k < 9; k++) v[k] = par_in_lds ? y[15 * pp + 6 + k] : readlane_d(ys, sb_base(pp) + k);
                     const double *Cc = Css + i * 81 + c9;       // column c9 of C_i
                     double s = 0;
 #pragma unroll
@@ -1126,7 +1066,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                     if (mine) ys -= s;
                 }
 #pragma unroll
-                for (int k = 0; k < 9; k++) v[k] = readlane_d2(ys, b + k);
+                for (int k = 0; k < 9; k++) v[k] = readlane_d(ys, b + k);
                 const double *Lc = Dss + i * 81 + c9;           // column c9 of L_i^-1
                 double x = 0;
 #pragma unroll
@@ -1143,7 +1083,7 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
         __syncthreads();
         if (wv < 2) {
             // (re-declared: the block barrier above must be reached by every wavefront)
-            PHASE_IDS();
+            ISV_PHASE_IDS();
             const int q9 = lane / 9, c9 = lane - 9 * q9;
             const int mynode = wv == 0 ? q9 : M + 1 + q9;
             const bool has = q9 < 7 && (wv == 0 ? mynode <= M : mynode <= N - 1);
@@ -1154,14 +1094,14 @@ DEV void build_solve_sb_body(const DevBatch &d, double *lds) {
                 const bool mine = has && mynode == i;
                 double v[9];
 #pragma unroll
-                for (int k = 0; k < 9; k++) v[k] = par_in_lds ? y[15 * pp + 6 + k] : readlane_d2(ys, sb_base(pp) + k);
+                for (int k = 0; k < 9; k++) v[k] = par_in_lds ? y[15 * pp + 6 + k] : readlane_d(ys, sb_base(pp) + k);
                 const double *Cc = Css + i * 81 + c9;           // column c9 of C_i
                 double s = 0;
 #pragma unroll
                 for (int k = 0; k < 9; k++) s += Cc[k * 9] * v[k];
                 if (mine) ys -= s;
 #pragma unroll
-                for (int k = 0; k < 9; k++) v[k] = readlane_d2(ys, b + k);
+                for (int k = 0; k < 9; k++) v[k] = readlane_d(ys, b + k);
                 const double *Lc = Dss + i * 81 + c9;           // column c9 of L_i^-1
                 double x = 0;
 #pragma unroll

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "isv_kernels.h"
 #include "isv_device_math.h"
+#include "isv_chain.h"
 
 // threads per window: 256 (4 wavefronts; four workgroups per CU) for N <= 11, 512 (8 wavefronts; two per CU) for long windows
 #define ST_THREADS(BIG) ((BIG) ? 512 : 256)
@@ -39,71 +40,12 @@
 #define ST_NO_YSPILL 1
 #endif
 
-DEV int st_sblk(int I, int J, int N) { return (J * N - J * (J - 1) / 2 + (I - J)) * 36; }   // I >= J
-DEV int st_pair(int a, int b) { return a * (a + 1) / 2 + b; }      // a >= b
-DEV int st_nlo(int i, int M) { return i > M ? i - 1 : 0; }
-DEV int st_nhi(int i, int M, int N) { return i < M ? i + 1 : N - 1; }
-
-DEV double st_readlane(double v, int lane) {
-    union { double d; int i[2]; } u; u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], lane);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
-    return u.d;
-}
-DEV double st_rsqrt(double x) {    // 1/sqrt(x) to ~1 ulp: hardware estimate + two Newton steps
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-#define ST_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 // a block barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding GLOBAL store of the wavefront (its
 // release fence covers all address spaces), i.e. for the acknowledgement of the chain pipeline's spills -- a memory round trip per
 // chain node on the critical path.  Used where no wavefront reads global data another one wrote since the last full barrier.
 #define ST_LDS_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
-#define ST_IDS() int t = t_outer; asm volatile("" : "+v"(t)); const int lane = t & 63; (void)lane
-
-// Factor the BS x BS SPD block at A (row-major, lower part valid) in registers and overwrite it with the INVERSE of its
-// Cholesky factor (lower, upper part zeroed).  One wavefront.  (k_build_solve_sb's routine.)
-template <int BS>
-DEV bool st_chol_inv(double *A, int lane) {
-    double row[BS], dinv[BS], x[BS];
-#pragma unroll
-    for (int k = 0; k < BS; k++) row[k] = (lane < BS) ? A[lane * BS + k] : 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < BS; j++) {
-        double s = row[j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= row[k] * st_readlane(row[k], j);
-        const double sj = st_readlane(s, j);               // pivot
-        if (!(sj > 0.0)) bad = true;
-        dinv[j] = st_rsqrt(sj);                            // 1 / L_jj (wave-uniform)
-        row[j] = (lane == j) ? sj * dinv[j] : s * dinv[j];
-    }
-#pragma unroll
-    for (int i = 0; i < BS; i++) {                          // lane c solves L x = e_c
-        double s = (lane == i) ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= st_readlane(row[k], i) * x[k];
-        x[i] = s * dinv[i];
-    }
-    ST_WSYNC();
-    if (lane < BS) {
-#pragma unroll
-        for (int k = 0; k < BS; k++) A[k * BS + lane] = x[k];   // x[k] = Linv[k][lane], zero for k < lane
-    }
-    ST_WSYNC();
-    return bad;
-}
 
 // ---- sizes ---------------------------------------------------------------------------------------------------------
-__host__ __device__ inline int st_ytot(int N) {
-    const int M = N / 2;
-    int o = 0;
-    for (int i = 0; i < N; i++) o += ((i < M ? i + 1 : N - 1) - (i > M ? i - 1 : 0) + 1) * 54;
-    return o;
-}
 // doubles of the chain work area: Y buffers (N + 1 block slots), per chain 4 D slots + 3 C slots; never smaller than what
 // the early phases stage there (prior blocks + u; the retry correction's dense w rows)
 __host__ __device__ inline int st_work_doubles(int N, int prior_H_sz) {
@@ -117,7 +59,7 @@ __host__ __device__ inline int st_work_doubles(int N, int prior_H_sz) {
 }
 // the global scratch of a window: L_i^-1 | C_i' | Y_i' (long windows, whose tile wavefronts read it; every window in the
 // ST_NO_YSPILL = 0 form) | the scaled init blocks of every node
-__host__ __device__ inline int st_ws_y(int N) { return (!ST_NO_YSPILL || N > 11) ? st_ytot(N) : 0; }
+__host__ __device__ inline int st_ws_y(int N) { return (!ST_NO_YSPILL || N > 11) ? chain_fill_doubles(N) : 0; }
 __host__ __device__ inline size_t st_ws_doubles(int N) { return (size_t)324 * N + (size_t)st_ws_y(N); }
 size_t build_solve_st_ws_doubles(int N) { return st_ws_doubles(N); }
 size_t build_solve_st_bytes(int N, int prior_H_sz) {
@@ -160,7 +102,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         const int t = t_outer;
         if (t == 0) {
             int o = 0;
-            for (int i = 0; i < N; i++) { yo[i] = o; o += (st_nhi(i, M, N) - st_nlo(i, M) + 1) * 54; }
+            for (int i = 0; i < N; i++) { yo[i] = o; o += (nhi(i, M, N) - nlo(i, M) + 1) * 54; }
             yo[N] = o; flag[0] = 0;
         }
         if (t < N - 1) skipL[t] = d.imu_skip[(size_t)w * (N - 1) + t];
@@ -208,25 +150,25 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
     auto HAp = [&](int i) { return H + (size_t)(i >= 1 ? i - 1 : 0) * ISV_IMU_H; };
     auto HBp = [&](int i) { return H + (size_t)(i <= N - 2 ? i : N - 2) * ISV_IMU_H; };
     auto rawD = [&](int i, int r, int c) -> double {       // sb_i x sb_i, r >= c
-        double v = HAp(i)[st_pair(21 + r, 21 + c)] * hasA(i);
-        v += HBp(i)[st_pair(6 + r, 6 + c)] * hasB(i);
-        const double pl = PH[PH_LIN9 + st_pair(r, c)];
+        double v = HAp(i)[pairidx(21 + r, 21 + c)] * hasA(i);
+        v += HBp(i)[pairidx(6 + r, 6 + c)] * hasB(i);
+        const double pl = PH[PH_LIN9 + pairidx(r, c)];
         if (i == d.Nvo - 1) v += pl;                       // Linear9Factor on the newest visual-odometry frame's speed/bias block
         if (d.est_ex && i == N - 1) v = r == c ? 1.0 : 0.0;   // the extrinsic's pseudo-frame: dummy unit block
         return v;
     };
     auto rawC = [&](int i, int a, int b) -> double {       // coupling of node i (column b) to its parent (row a)
-        if (i < M) return H[(size_t)i * ISV_IMU_H + st_pair(21 + a, 6 + b)] * (skipL[i] ? 0.0 : 1.0);               // parent i + 1: factor i
-        return H[(size_t)(i - 1) * ISV_IMU_H + st_pair(21 + b, 6 + a)] * (skipL[i - 1] ? 0.0 : 1.0);              // parent i - 1: factor i - 1
+        if (i < M) return H[(size_t)i * ISV_IMU_H + pairidx(21 + a, 6 + b)] * (skipL[i] ? 0.0 : 1.0);               // parent i + 1: factor i
+        return H[(size_t)(i - 1) * ISV_IMU_H + pairidx(21 + b, 6 + a)] * (skipL[i - 1] ? 0.0 : 1.0);              // parent i - 1: factor i - 1
     };
     auto rawY = [&](int i, int pz, int r, int c) -> double {      // pose_pz (row r) x sb_i (column c), pz in {i - 1, i, i + 1}
         if (pz == i) {
-            double v = HAp(i)[st_pair(21 + c, 15 + r)] * hasA(i);
-            v += HBp(i)[st_pair(6 + c, r)] * hasB(i);
+            double v = HAp(i)[pairidx(21 + c, 15 + r)] * hasA(i);
+            v += HBp(i)[pairidx(6 + c, r)] * hasB(i);
             return v;
         }
-        if (pz == i + 1) return H[(size_t)(i <= N - 2 ? i : N - 2) * ISV_IMU_H + st_pair(15 + r, 6 + c)] * hasB(i);
-        return H[(size_t)(i >= 1 ? i - 1 : 0) * ISV_IMU_H + st_pair(21 + c, r)] * hasA(i);
+        if (pz == i + 1) return H[(size_t)(i <= N - 2 ? i : N - 2) * ISV_IMU_H + pairidx(15 + r, 6 + c)] * hasB(i);
+        return H[(size_t)(i >= 1 ? i - 1 : 0) * ISV_IMU_H + pairidx(21 + c, r)] * hasA(i);
     };
 
     for (;;) {
@@ -250,8 +192,8 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             const int ev = r < 6 ? 6 * I + r : 0;
             const double v0 = V[nS + ev], v1 = V[nS + n6 + ev], v2 = V[nS + 2 * n6 + ev];
             // diagonal of the IMU factors' J^T J
-            double vd = HAp(I)[st_pair(15 + r, 15 + r)] * hasA(I);
-            vd += HBp(I)[st_pair(r, r)] * hasB(I);
+            double vd = HAp(I)[pairidx(15 + r, 15 + r)] * hasA(I);
+            vd += HBp(I)[pairidx(r, r)] * hasB(I);
             if (r < 6) { D[e] = v0 + vd; g[e] = v1 + vg; y[e] = v2; }
             else { D[e] = vd; g[e] = vg; y[e] = 0.0; }
         }
@@ -310,12 +252,12 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         for (int e = t; e < N * 21 + (N - 1) * 36; e += LT) {
             if (e < N * 21) {
                 const int I = e / 21, q = e - 21 * I, r = triAB[2 * q], c = triAB[2 * q + 1];
-                double v = HAp(I)[st_pair(15 + r, 15 + c)] * hasA(I);
-                v += HBp(I)[st_pair(r, c)] * hasB(I);
-                Spp[st_sblk(I, I, N) + r * 6 + c] += v;
+                double v = HAp(I)[pairidx(15 + r, 15 + c)] * hasA(I);
+                v += HBp(I)[pairidx(r, c)] * hasB(I);
+                Spp[sblk(I, I, N) + r * 6 + c] += v;
             } else {
                 const int q0 = e - N * 21, I = q0 / 36, q = q0 - 36 * I, r = q / 6, c = q - 6 * r;
-                Spp[st_sblk(I + 1, I, N) + q] += H[(size_t)I * ISV_IMU_H + st_pair(15 + r, c)] * (skipL[I] ? 0.0 : 1.0);
+                Spp[sblk(I + 1, I, N) + q] += H[(size_t)I * ISV_IMU_H + pairidx(15 + r, c)] * (skipL[I] ? 0.0 : 1.0);
             }
         }
         __syncthreads();
@@ -338,7 +280,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                     const int ga = (aa < 6 || ncol != 12) ? c0 + aa : c1 + aa - 6;
                     const int gb = (bb < 6 || ncol != 12) ? c0 + bb : c1 + bb - 6;
                     const int Ia = ga / 15, ra = ga - 15 * Ia, Ib = gb / 15, rb = gb - 15 * Ib;
-                    if (ra < 6) Spp[st_sblk(Ia, Ib, N) + ra * 6 + rb] += v;
+                    if (ra < 6) Spp[sblk(Ia, Ib, N) + ra * 6 + rb] += v;
                     if (aa == bb) D[ga] += v;
                 } else {
                     const int aa = e - np2;
@@ -521,7 +463,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                     const int Rr = 16 * TI + kq + 4 * reg, Cc = 16 * TJ + i16;
                     if (Rr < R && Cc <= Rr && !(skipPM && Rr < 6)) {
                         const int pI = Rr / 6, r = Rr - 6 * pI, pJ = Cc / 6, c = Cc - 6 * pJ;
-                        Spp[st_sblk(P0 + pI, P0 + pJ, N) + r * 6 + c] -= acc[reg];
+                        Spp[sblk(P0 + pI, P0 + pJ, N) + r * 6 + c] -= acc[reg];
                     }
                 }
             }
@@ -533,7 +475,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         // nodes ahead (D, C, the parent's own pose x speed/bias blocks) are REQUESTED at the top of the step and land in LDS at its
         // end: their memory latency runs behind the LDS work.  One block barrier per node.
         {
-            ST_IDS();
+            ISV_PHASE_IDS();
             const int cntF = M, cntB = N - 1 - M;
             auto Dslot = [&](int ch, int i) { return Dring + (ch * 4 + (i & 3)) * 81; };
             auto Cslot = [&](int ch, int i) { return Cring + (ch * 3 + (i % 3)) * 81; };
@@ -555,7 +497,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             __syncthreads();
             auto crit = [&](int ch, int i) {
                 double *Di = Dslot(ch, i), *Ci = Cslot(ch, i);
-                if (st_chol_inv<9>(Di, lane)) { if (lane == 0) flag[0] = 1; return; }
+                if (chol_inv_block<9>(Di, lane)) { if (lane == 0) flag[0] = 1; return; }
                 if (lane < 10) {                                   // C_i' = C_i L_i^-T (9 rows), z_i^T = y_i^T L_i^-T
                     double *ptr = lane < 9 ? Ci + lane * 9 : y + 15 * i + 6;
                     double v[9], o[9];
@@ -571,7 +513,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
 #pragma unroll
                     for (int k = 0; k < 9; k++) ptr[k] = o[k];
                 }
-                ST_WSYNC();
+                ISV_WSYNC();
                 const int pp = ch == 0 ? i + 1 : i - 1;
                 if (pp == M) return;                               // both chains end in M: applied after the loop
                 double *Dp = Dslot(ch, pp);
@@ -588,13 +530,13 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                     for (int k = 0; k < 9; k++) s += Ci[r * 9 + k] * y[15 * i + 6 + k];
                     y[15 * pp + 6 + r] -= s;
                 }
-                ST_WSYNC();
+                ISV_WSYNC();
             };
             // Y-work of node j by ONE wavefront (nothing stays in registers across its stages).  A child of M (last = true) forms no
             // parent; the BACKWARD child also leaves pose block (M, M) and pose M's rhs to the join: the forward child updates them in
             // the same step.
             auto ywork = [&](int ch, int j, bool last) {
-                const int lo = st_nlo(j, M), hi = st_nhi(j, M, N), nr = hi - lo + 1, s0 = lo + ch;       // first slot
+                const int lo = nlo(j, M), hi = nhi(j, M, N), nr = hi - lo + 1, s0 = lo + ch;       // first slot
                 const double *Lj = Dslot(ch, j), *Cj = Cslot(ch, j);
                 double *Yg = gY + yo[j]; (void)Yg;
                 // spill L_j^-1 and C_j' (final since the critical path left node j)
@@ -618,7 +560,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                         for (int k = 0; k < 9; k++) Yg[k * (6 * nr) + rho] = o[k];                       // global: column-major per node
                     }
                 }
-                ST_WSYNC();
+                ISV_WSYNC();
                 {   // pose rhs -= Y_j' z_j, then the pose blocks' downdate
                     const bool deferM = last && ch == 1;             // (lo == M there: pose M's rhs rows are the forward child's in this step)
                     for (int rr = lane; rr < 6 * nr; rr += 64) {
@@ -636,7 +578,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                     if constexpr (!BIG) yyt_tiles([&](int row) { return (s0 * 6 + row) * 9; }, Ybuf, 6 * nr, 9, lo, 0, 1, deferM, lane);
                 }
                 if (last) return;
-                ST_WSYNC();
+                ISV_WSYNC();
                 for (int rho = lane; rho < 6 * nr; rho += 64) {      // parent row rho: - Y'[rho] C_j'^T, in place
                     double *ptr = Ybuf + (s0 * 6 + rho) * 9;
                     double o[9], q9v[9];
@@ -652,7 +594,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
 #pragma unroll
                     for (int c = 0; c < 9; c++) ptr[c] = q9v[c];
                 }
-                ST_WSYNC();
+                ISV_WSYNC();
             };
             const int steps = (cntF > cntB ? cntF : cntB) + 1;
             for (int k = 0; k < steps; k++) {
@@ -706,7 +648,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                         const int ch = (wv - 4) >> 1, half = (wv - 4) & 1, cnt = ch == 0 ? cntF : cntB, kk = k - 2;
                         if (kk >= 0 && kk < cnt - 1) {
                             const int j = ch == 0 ? kk : N - 1 - kk;
-                            const int lo = st_nlo(j, M), nr = st_nhi(j, M, N) - lo + 1, R = 6 * nr;
+                            const int lo = nlo(j, M), nr = nhi(j, M, N) - lo + 1, R = 6 * nr;
                             const double *Yg = gY + yo[j];
                             const int T = (R + 15) >> 4, ntile = T * (T + 1) / 2;
                             const int i16 = lane & 15, kq = lane >> 4;
@@ -732,7 +674,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                                     const int Rr = 16 * TI + kq + 4 * reg, Cc = 16 * TJ + i16;
                                     if (Rr < R && Cc <= Rr) {
                                         const int pI = Rr / 6, r = Rr - 6 * pI, pJ = Cc / 6, c = Cc - 6 * pJ;
-                                        Spp[st_sblk(lo + pI, lo + pJ, N) + r * 6 + c] -= acc[reg];
+                                        Spp[sblk(lo + pI, lo + pJ, N) + r * 6 + c] -= acc[reg];
                                     }
                                 }
                             }
@@ -753,7 +695,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                     for (int ch = 0; ch < 2; ch++) {
                         const int cnt = ch == 0 ? cntF : cntB;
                         if (cnt >= 1) {
-                            const int j = ch == 0 ? M - 1 : M + 1, lo = st_nlo(j, M), nr = st_nhi(j, M, N) - lo + 1, s0 = lo + ch;
+                            const int j = ch == 0 ? M - 1 : M + 1, lo = nlo(j, M), nr = nhi(j, M, N) - lo + 1, s0 = lo + ch;
                             yyt_tiles([&](int row) { return (s0 * 6 + row) * 9; }, Ybuf, 6 * nr, 9, lo, wv, NW, ch == 1, lane);
                         }
                         __syncthreads();
@@ -764,7 +706,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         STSTAMP(4);
         if (!flag[0]) {
             // ---- the join: what the backward child left of pose block (M, M), then node M -----------------------------------
-            ST_IDS();
+            ISV_PHASE_IDS();
             auto Dslot = [&](int ch, int i) { return Dring + (ch * 4 + (i & 3)) * 81; };
             auto Cslot = [&](int ch, int i) { return Cring + (ch * 3 + (i % 3)) * 81; };
             auto slotM = [&](int pz) { return pz <= M ? pz : pz + 1; };
@@ -779,7 +721,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                         double s = 0;
 #pragma unroll
                         for (int k = 0; k < 9; k++) s += YM[r * 9 + k] * YM[c * 9 + k];
-                        Spp[st_sblk(M, M, N) + r * 6 + c] -= s;
+                        Spp[sblk(M, M, N) + r * 6 + c] -= s;
                     }
                 } else if (lane < 42) {
                     const int r = lane - 36;
@@ -807,8 +749,8 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                         y[15 * M + 6 + r] -= s;
                     }
                 }
-                ST_WSYNC();
-                if (st_chol_inv<9>(DM, lane)) { if (lane == 0) flag[0] = 1; }
+                ISV_WSYNC();
+                if (chol_inv_block<9>(DM, lane)) { if (lane == 0) flag[0] = 1; }
                 else if (lane == 0) {                            // z_M
                     double v[9], o[9];
 #pragma unroll
@@ -901,15 +843,15 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         STSTAMP(5);
         if (!flag[0]) {
             // ---- blocked Cholesky of the pose system (6x6 blocks; diagonal blocks hold L_JJ^-1 afterwards), look-ahead on wavefront 0
-            ST_IDS();
-            if (wv == 0 && st_chol_inv<6>(Spp + st_sblk(0, 0, N), lane)) { if (lane == 0) flag[0] = 1; }
+            ISV_PHASE_IDS();
+            if (wv == 0 && chol_inv_block<6>(Spp + sblk(0, 0, N), lane)) { if (lane == 0) flag[0] = 1; }
             __syncthreads();
             for (int J = 0; J < N; J++) {
                 if (flag[0]) break;
                 const int m = N - J - 1;
-                const double *Li = Spp + st_sblk(J, J, N);
+                const double *Li = Spp + sblk(J, J, N);
                 for (int rr = t; rr < m * 6 + 1; rr += LT) {    // panel rows: X = A L_JJ^-T; last row = rhs (z_J)
-                    double *A = rr < m * 6 ? Spp + st_sblk(J + 1, J, N) + rr * 6 : y + 15 * J;   // blocks (J+1.., J) are contiguous
+                    double *A = rr < m * 6 ? Spp + sblk(J + 1, J, N) + rr * 6 : y + 15 * J;   // blocks (J+1.., J) are contiguous
                     double v[6], o[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) v[k] = A[k];
@@ -925,8 +867,8 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 }
                 __syncthreads();
                 if (m == 0) break;
-                const int e0 = st_sblk(J + 1, J + 1, N), cntT = m * (m + 1) / 2 * 36;
-                const double *X = Spp + st_sblk(J + 1, J, N);       // X_I at (I - J - 1) * 36
+                const int e0 = sblk(J + 1, J + 1, N), cntT = m * (m + 1) / 2 * 36;
+                const double *X = Spp + sblk(J + 1, J, N);       // X_I at (I - J - 1) * 36
                 auto trailing_entry = [&](int e) {
                     if (e >= cntT) {                             // rhs rows: y_I -= X_I z_J
                         const int rr = e - cntT;
@@ -949,8 +891,8 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 };
                 if (wv == 0) {
                     if (lane < 36) trailing_entry(lane);         // block (J+1, J+1) is the first of the trailing storage
-                    ST_WSYNC();
-                    if (st_chol_inv<6>(Spp + e0, lane)) { if (lane == 0) flag[0] = 1; }
+                    ISV_WSYNC();
+                    if (chol_inv_block<6>(Spp + e0, lane)) { if (lane == 0) flag[0] = 1; }
                 } else {
                     const int nit = (m * (m + 1) / 2 - 1) * 6;         // 2 x 3 sub-blocks of the trailing blocks after the first one
                     for (int it = t - 64; it < nit + m * 6; it += LT - 64) {
@@ -992,7 +934,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         // ---- backward substitution (the forward one rode along with the factorisations) ------------------------------------
         // pose block: one wavefront, right-hand side in REGISTERS (k_build_solve_sb's routine)
         if (wv == 0) {
-            ST_IDS();
+            ISV_PHASE_IDS();
             const int q6 = lane / 6, c6 = lane - 6 * q6;
             const int fA = q6, fB = 10 + q6;                    // my frame in yp0 / yp1
             const bool hasPA = q6 < 10 && fA < N, hasPB = q6 < 10 && fB < N;
@@ -1001,21 +943,21 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 const int b = 6 * (J % 10);
                 double v[6];
 #pragma unroll
-                for (int k = 0; k < 6; k++) v[k] = J < 10 ? st_readlane(yp0, b + k) : st_readlane(yp1, b + k);
-                const double *Lc = Spp + st_sblk(J, J, N) + c6;    // column c6 of L_JJ^-1
+                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d(yp0, b + k) : readlane_d(yp1, b + k);
+                const double *Lc = Spp + sblk(J, J, N) + c6;    // column c6 of L_JJ^-1
                 double x = 0;
 #pragma unroll
                 for (int k = 0; k < 6; k++) x += Lc[k * 6] * v[k];
                 if (J < 10) { if (hasPA && fA == J) yp0 = x; } else { if (hasPB && fB == J) yp1 = x; }
 #pragma unroll
-                for (int k = 0; k < 6; k++) v[k] = J < 10 ? st_readlane(yp0, b + k) : st_readlane(yp1, b + k);
+                for (int k = 0; k < 6; k++) v[k] = J < 10 ? readlane_d(yp0, b + k) : readlane_d(yp1, b + k);
                 if (hasPA && fA < J) {
-                    const double *Lb = Spp + st_sblk(J, fA, N) + c6;
+                    const double *Lb = Spp + sblk(J, fA, N) + c6;
 #pragma unroll
                     for (int k = 0; k < 6; k++) yp0 -= Lb[k * 6] * v[k];
                 }
                 if (N > 10 && hasPB && fB < J) {
-                    const double *Lb = Spp + st_sblk(J, fB, N) + c6;
+                    const double *Lb = Spp + sblk(J, fB, N) + c6;
 #pragma unroll
                     for (int k = 0; k < 6; k++) yp1 -= Lb[k * 6] * v[k];
                 }
@@ -1035,7 +977,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             // every node's C_i' and L_i^-1 come back from the global scratch with ONE coalesced sweep -- into the (dead) chain buffers
             // (162 N doubles fit them up to N = 11: st_work_doubles), or, for long windows, over the pose blocks: the pose system's
             // factor is dead once x_pose is known -- then the nodes run out of LDS
-            ST_IDS();
+            ISV_PHASE_IDS();
             double *stg = BIG ? Spp : work;
             double *sDi = stg, *sC = stg + 81 * N;
             double *ev = BIG ? Spp + 162 * N : Spp, *vv = ev + 9 * N, *pt = vv + 9 * N;       // e_i, v_i [9 N], the fold's parts [27 N]: over the dead pose blocks
@@ -1068,10 +1010,10 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 }
                 double v = 0;
 #pragma unroll
-                for (int k = 0; k < 9; k++) v += sDi[i * 81 + cl * 9 + k] * st_readlane(wr, k);      // (L^-1 is lower: the upper part is stored as zeros)
-                ST_WSYNC();
+                for (int k = 0; k < 9; k++) v += sDi[i * 81 + cl * 9 + k] * readlane_d(wr, k);      // (L^-1 is lower: the upper part is stored as zeros)
+                ISV_WSYNC();
                 if (lane < 9) { vv[9 * i + lane] = v; y[15 * i + 6 + lane] -= v; }
-                ST_WSYNC();
+                ISV_WSYNC();
             };
             auto node_bwd = [&](int i, int pp) {
                 double sv = y[15 * i + 6 + cl];
@@ -1081,10 +1023,10 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 }
                 double x = 0;
 #pragma unroll
-                for (int k = 0; k < 9; k++) x += sDi[i * 81 + k * 9 + cl] * st_readlane(sv, k);
-                ST_WSYNC();
+                for (int k = 0; k < 9; k++) x += sDi[i * 81 + k * 9 + cl] * readlane_d(sv, k);
+                ISV_WSYNC();
                 if (lane < 9) y[15 * i + 6 + lane] = x;
-                ST_WSYNC();
+                ISV_WSYNC();
             };
             // (run-time N: ONE loop for both chains with per-lane selects, as in the elimination.  Written as two loops under
             //  `if (wv == 0) .. else if (wv == 1)`, or as one loop on a readfirstlane'd wavefront index, the run-time-N instantiation gave
@@ -1109,10 +1051,10 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         // chain rhs -= Y_i'^T x_pose from the global scratch (column-major per node: a thread reads contiguous rows);
         // thread = (speed/bias row, quarter of the pose blocks), folded in fixed order through the work area
         {
-            ST_IDS();
+            ISV_PHASE_IDS();
             double *part = work;                                   // [36 N] (the chain buffers are dead)
             for (int tq = t; tq < 36 * N; tq += LT) {
-                const int o = tq >> 2, prt = tq & 3, i = o / 9, c = o - 9 * i, lo = st_nlo(i, M), nr = st_nhi(i, M, N) - lo + 1;
+                const int o = tq >> 2, prt = tq & 3, i = o / 9, c = o - 9 * i, lo = nlo(i, M), nr = nhi(i, M, N) - lo + 1;
                 const double *Yc = gY + yo[i] + c * (6 * nr);
                 double s = 0;
                 for (int a = prt; a < nr; a += 4) {
@@ -1138,7 +1080,7 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             // every node's C_i' and L_i^-1 come back from the global scratch with ONE coalesced sweep -- into the (dead) chain buffers
             // (162 N doubles fit them up to N = 11: st_work_doubles), or, for long windows, over the pose blocks: the pose system's
             // factor is dead once x_pose is known -- then the nodes run out of LDS
-            ST_IDS();
+            ISV_PHASE_IDS();
             double *stg = BIG ? Spp : work;
             double *sDi = stg, *sC = stg + 81 * N;
             for (int e = t; e < 162 * N; e += LT) stg[e] = ws[e];          // gDinv | gC are contiguous in the scratch
@@ -1152,10 +1094,10 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
                 }
                 double x = 0;
 #pragma unroll
-                for (int k = 0; k < 9; k++) x += sDi[i * 81 + k * 9 + cl] * st_readlane(sv, k);
-                ST_WSYNC();
+                for (int k = 0; k < 9; k++) x += sDi[i * 81 + k * 9 + cl] * readlane_d(sv, k);
+                ISV_WSYNC();
                 if (lane < 9) y[15 * i + 6 + lane] = x;
-                ST_WSYNC();
+                ISV_WSYNC();
             };
             if (wv == 0) node_bwd(M, -1);
             __syncthreads();

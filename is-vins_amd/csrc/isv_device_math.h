@@ -1,4 +1,4 @@
-// isv_device_math.h -- fp64 3x3 / quaternion / SO(3) helpers for the gfx950 kernels.
+// isv_device_math.h -- wave-level primitives and fp64 3x3 / quaternion / SO(3) helpers for the gfx950 kernels.
 // Semantics follow the Eigen / Sophus / Utility calls the reference factors make
 // (include/utility/utility.h:11-110, include/utility/sophus_utils.hpp:194-236); written for
 // registers: everything is passed by value or small local arrays that the compiler keeps in VGPRs.
@@ -8,6 +8,69 @@
 #define DEV __device__ __forceinline__
 // wave-level ordering of LDS traffic (LDS executes one wavefront's accesses in issue order)
 #define ISV_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+// a fresh, opaque copy of the thread id t_outer per phase: index arithmetic is then recomputed where it is used instead of being
+// shared across phases by CSE -- the shared values live through the whole kernel and spill under the 128-VGPR cap, and
+// every reload is a scratch (global memory) round trip on the serial path
+#define ISV_PHASE_IDS() int t = t_outer; asm volatile("" : "+v"(t)); const int lane = t & 63; (void)lane
+
+// ---- wave-level helpers ---------------------------------------------------------------------------------------------
+DEV double readlane_d(double v, int lane) {   // v of lane `lane`, wave-uniform
+    union { double d; int i[2]; } u; u.d = v;
+    u.i[0] = __builtin_amdgcn_readlane(u.i[0], lane);
+    u.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
+    return u.d;
+}
+DEV double rsqrt_nr2(double x) {   // 1/sqrt(x) to ~1 ulp: hardware estimate + two Newton steps (no f64 sqrt / divide sequences)
+    double r = __builtin_amdgcn_rsq(x);
+    r = r * (1.5 - 0.5 * x * r * r);
+    r = r * (1.5 - 0.5 * x * r * r);
+    return r;
+}
+// deterministic wave sum / max (fixed butterfly; every lane ends with the result)
+DEV double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+DEV double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+// Factor the BS x BS SPD block at A (row-major, leading dimension BS, lower part valid) in registers and
+// overwrite it with the INVERSE of its Cholesky factor (lower, upper part zeroed).  One wavefront.  Returns true if
+// a pivot was not positive (the block is not SPD).
+template <int BS>
+DEV bool chol_inv_block(double *A, int lane) {
+    double row[BS], dinv[BS], x[BS];
+#pragma unroll
+    for (int k = 0; k < BS; k++) row[k] = (lane < BS) ? A[lane * BS + k] : 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < BS; j++) {
+        double s = row[j];
+#pragma unroll
+        for (int k = 0; k < j; k++) s -= row[k] * readlane_d(row[k], j);
+        const double sj = readlane_d(s, j);                // pivot
+        if (!(sj > 0.0)) bad = true;
+        dinv[j] = rsqrt_nr2(sj);                            // 1 / L_jj (wave-uniform)
+        row[j] = (lane == j) ? sj * dinv[j] : s * dinv[j];
+    }
+#pragma unroll
+    for (int i = 0; i < BS; i++) {                          // lane c solves L x = e_c
+        double s = (lane == i) ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; k++) s -= readlane_d(row[k], i) * x[k];
+        x[i] = s * dinv[i];
+    }
+    ISV_WSYNC();
+    if (lane < BS) {
+#pragma unroll
+        for (int k = 0; k < BS; k++) A[k * BS + lane] = x[k];   // x[k] = Linv[k][lane], zero for k < lane
+    }
+    ISV_WSYNC();
+    return bad;
+}
 
 struct Quat { double w, x, y, z; };
 

@@ -10,7 +10,6 @@ __host__ __device__ inline int tvis_col2(int a, int N) { return 36 * (a * N - a 
 typedef double double4g __attribute__((ext_vector_type(4)));
 // LDS row of one factor: r(2) J_i(12) J_j(12) [+ J_ex(12) when the extrinsic is estimated] + 1 (odd stride)
 __host__ __device__ constexpr int lg_xld(bool ex) { return ex ? 39 : 27; }
-#define LGSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // LGW wavefronts per window: 4 for batches (158 VGPRs -> three workgroups per CU), 8 while every window has a CU of its own
 // (twice the wavefronts on the factor stream; which wavefront sums a pair group does not change the sums)
@@ -186,7 +185,7 @@ DEV void lin_gram_body(const DevBatch &d, double *lds) {
                     for (int k = 0; k < 12; k++) row[26 + k] = Jex[k];
                 }
             }
-            LGSYNC();
+            ISV_WSYNC();
             LGSTAMP(57);
             double v[8], vx[8];
 #pragma unroll
@@ -225,7 +224,7 @@ DEV void lin_gram_body(const DevBatch &d, double *lds) {
                 }
             }
             LGSTAMP(59);
-            LGSYNC();
+            ISV_WSYNC();
         }
         LGSTAMP(27);
     }

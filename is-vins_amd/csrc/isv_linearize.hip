@@ -655,13 +655,6 @@ __global__ __launch_bounds__(256) void k_imu_raw(DevBatch d, const double *pose_
 }
 
 typedef double double4i __attribute__((ext_vector_type(4)));
-DEV double imu_lane_value(double v, int lane) {
-    union { double d; int i[2]; } u;
-    u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], lane);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
-    return u.d;
-}
 // where entry (row, col) of the dense [16][32] operand [J | r | 0] comes from: >= 0 compact value j, -1 zero, -2 / -3 the constants -1 / +1
 // (3x3 block map of include/factor/imu_factor.h:66-155; block rows: p, q, v, ba, bg; block columns: p_i q_i v_i ba_i bg_i p_j q_j v_j ba_j bg_j)
 __constant__ short c_imu_block_of[5][10] = {{16, 25, 52, 61, 70, 115, -1, -1, -1, -1},
@@ -726,7 +719,7 @@ DEV void imu_weight_factor(const DevBatch &d, int f, const double (&sv)[4], cons
         // 0.5 |Jw[:, 30]|^2, rows in order (no loss function on IMU factors, :1050): row k sits in lane 14 + 16 (k & 3), register k >> 2 of tile 1
         double s = 0;
 #pragma unroll
-        for (int k = 0; k < 15; k++) { const double v = imu_lane_value(a1[k >> 2], 14 + 16 * (k & 3)); s += v * v; }
+        for (int k = 0; k < 15; k++) { const double v = readlane_d(a1[k >> 2], 14 + 16 * (k & 3)); s += v * v; }
         if (lane == 0) cost_out[f] = 0.5 * s;
     }
     // packed J^T J (pairs a >= b at a(a+1)/2 + b, a, b < 30) then J^T r (row 30 of H)

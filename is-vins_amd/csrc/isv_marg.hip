@@ -25,9 +25,6 @@
 #endif
 #define SYNC() __syncthreads()
 
-DEV double m_rsqrt(double x) { double r = __builtin_amdgcn_rsq(x); r = r * (1.5 - 0.5 * x * r * r); r = r * (1.5 - 0.5 * x * r * r); return r; }
-DEV double m_rcp(double x) { double r = __builtin_amdgcn_rcp(x); r = r * (2.0 - x * r); r = r * (2.0 - x * r); return r; }
-
 // The arithmetic of one Jacobi rotation, written with explicit fma() so that every instance (the one-wavefront loops, the
 // four-wavefront kernel) rounds the same way whatever the compiler would have contracted: their results are bitwise equal.
 DEV double jr_rsqrt(double x) { double r = __builtin_amdgcn_rsq(x); const double h = 0.5 * x; r = r * fma(-(h * r), r, 1.5); r = r * fma(-(h * r), r, 1.5); return r; }
@@ -836,9 +833,6 @@ __global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
         RECOVER(17, 3, no_dst);
         RECOVER(20, 1, no_dst);
 #undef RECOVER
-#if defined(MARG_STOP) && MARG_STOP == 3
-        return;
-#endif
         MSTAMP(7);
         // zero test / KLD (estimator.cpp:1519-1534): A = (Jr U)^T X (Jr U) over the kept eigenpairs vs D
         int rank = 0; for (int k = 0; k < 21; k++) rank += keep[k];

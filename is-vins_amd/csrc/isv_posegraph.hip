@@ -33,10 +33,9 @@
 #include "isv_device_math.h"
 #include "isv_prior_factor.h"
 
-#define PG_WSYNC() ISV_WSYNC()
 // LDS-only ordering inside the wavefront (the 6x6 tiles T0 / T1 / T2): the LDS executes one wavefront's accesses in issue order,
 // so all that is needed is that the compiler neither reorders them nor keeps tile values in registers.  Unlike a release
-// fence this does NOT wait for outstanding global loads and stores (vmcnt): with PG_WSYNC every step of the factorisation
+// fence this does NOT wait for outstanding global loads and stores (vmcnt): with ISV_WSYNC every step of the factorisation
 // paid the latency of its own L-block store and of the next row's prefetch.
 #define PG_LSYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
 // make this wavefront's global stores visible to its own later loads (other lanes read what a lane wrote)
@@ -77,19 +76,8 @@ struct PgDev {
 };
 
 // ---- 6x6 helpers: lane e < 36 owns element (a, b) = (e / 6, e % 6) -------------------------------------------------
-DEV double readlane_d(double v, int lane) {
-    union { double d; int i[2]; } u; u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], lane);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], lane);
-    return u.d;
-}
-DEV double pg_rsqrt(double x) {                       // 1/sqrt(x) to ~1 ulp: hardware estimate + two Newton steps (no f64 sqrt / divide sequences on the serial path)
-    double r = __builtin_amdgcn_rsq(x);
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-// D (6x6 SPD, row-major in LDS tile T, lower part valid) -> T = inverse of its Cholesky factor (lower); returns false if not SPD
+// D (6x6 SPD, row-major in LDS tile T, lower part valid) -> T = inverse of its Cholesky factor (lower); returns false if not SPD.
+// chol_inv_block<6> (isv_device_math.h) with PG_LSYNC instead of ISV_WSYNC, whose fences would also wait for global memory.
 DEV bool pg_chol_inv6(double *T, int lane) {
     double row[6], dinv[6], x[6];
 #pragma unroll
@@ -102,7 +90,7 @@ DEV bool pg_chol_inv6(double *T, int lane) {
         for (int k = 0; k < j; k++) s -= row[k] * readlane_d(row[k], j);
         const double sj = readlane_d(s, j);
         if (!(sj > 0.0)) bad = true;
-        dinv[j] = pg_rsqrt(sj);
+        dinv[j] = rsqrt_nr2(sj);
         row[j] = (lane == j) ? sj * dinv[j] : s * dinv[j];
     }
 #pragma unroll
@@ -119,17 +107,6 @@ DEV bool pg_chol_inv6(double *T, int lane) {
     }
     PG_LSYNC();
     return !bad;
-}
-// deterministic wave sum (fixed butterfly)
-DEV double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-DEV double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
 }
 
 // RelativePoseFactor::Evaluate (include/factor/relative_pose_factor.h:27-70) / RollPitchFactor::Evaluate
@@ -271,7 +248,7 @@ __global__ __launch_bounds__(64 * NW) void k_pgo(PgDev dv) {
         for (int q = tid; q < nf; q += NT) { dyn_idx[q] = start[q]; dyn_idx[IR + q] = rowptr[q]; }
         for (int q = tid; q <= nf; q += NT) dyn_idx[2 * IR + q] = colptr[q];
         for (int q = tid; q < nc; q += NT) dyn_idx[3 * IR + 1 + q] = colrows[q];
-        if constexpr (NW > 1) __syncthreads(); else PG_WSYNC();
+        if constexpr (NW > 1) __syncthreads(); else ISV_WSYNC();
     }
     // (explicit LDS reads: a pointer that may be LDS or global becomes a FLAT access, which waits for every outstanding
     //  global load and store as well)

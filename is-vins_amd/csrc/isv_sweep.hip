@@ -267,10 +267,6 @@ DEV void sweep_split_body(DevBatch &d, const int grp, const int Gs, const int nw
 template <int NT, int TPW>
 __global__ __launch_bounds__(64 * ((NT * (NT + 1) / 2 + TPW - 1) / TPW)) void k_schur_split(DevBatch d, int Gs, int GrMax) {
     constexpr int nwaves = (NT * (NT + 1) / 2 + TPW - 1) / TPW;
-#ifdef ISV_SPLIT_SKIP          /* timing experiment: 1 = no direct part, 2 = no downdates (results are wrong) */
-    if (ISV_SPLIT_SKIP == 1 && (int)blockIdx.y < Gs) return;
-    if (ISV_SPLIT_SKIP == 2 && (int)blockIdx.y >= Gs) return;
-#endif
     if ((int)blockIdx.y < Gs) sweep_split_body(d, blockIdx.y, Gs, nwaves);
     else rank1_body<NT, TPW, 64, 1, false, true>(d, (int)blockIdx.y - Gs, GrMax);
 }
