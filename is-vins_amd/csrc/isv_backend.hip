@@ -29,9 +29,10 @@ extern "C" void isv_backend_destroy(isv_backend_t *h) {
     if (h->seq && h->seq_free) h->seq_free(h->seq);
     if (h->init_scratch) (void)hipFree(h->init_scratch);
     if (h->init_kld) (void)hipFree(h->init_kld);
-    if (h->free_align) h->free_align(h);
-    if (h->free_sfm) h->free_sfm(h);
-    if (h->free_relpose) h->free_relpose(h);
+    for (InitSlot &s : h->init_slot) {
+        if (s.d) (void)hipFree(s.d);
+        for (auto &e : s.ev) if (e) (void)hipEventDestroy(e);
+    }
     for (void *p : h->allocs) (void)hipFree(p);
     for (void *p : h->hallocs) (void)hipHostFree(p);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);

@@ -16,6 +16,16 @@
         }                                                                                        \
     } while (0)
 
+// the batched initialisation stages (isv_init_launch.h runs them): isv_internal_visual_imu_align_batch (isv_initial.hip),
+// isv_internal_sfm_batch (isv_sfm.hip), isv_internal_relpose_batch (isv_relpose.hip)
+enum { ISV_INIT_ALIGN, ISV_INIT_SFM, ISV_INIT_RELPOSE, ISV_INIT_STAGES };
+// a stage's state on the handle: its device block (grow-only, freed with the handle), its kernel events, its last call's times
+struct InitSlot {
+    void *d = nullptr; size_t cap = 0;
+    hipEvent_t ev[2] = {};
+    double call_ms = 0, kernel_ms = 0;
+};
+
 struct isv_backend {
     isv_config_t cfg;
     std::string err;
@@ -58,21 +68,7 @@ struct isv_backend {
     int device = 0;               // the HIP device the handle was created on; every entry point re-selects it
     double *init_scratch = nullptr, *init_kld = nullptr;   // initFactorGraph scratch, allocated on first use and kept
     size_t init_cap = 0;
-    // isv_internal_visual_imu_align_batch (isv_initial.hip): its device block (grow-only), kernel events, last call's times
-    void *align_d = nullptr; size_t align_cap = 0;
-    hipEvent_t align_ev[2] = {};
-    double align_call_ms = 0, align_kernel_ms = 0;
-    void (*free_align)(isv_backend *) = nullptr;
-    // isv_internal_sfm_batch (isv_sfm.hip): the same pattern
-    void *sfm_d = nullptr; size_t sfm_cap = 0;
-    hipEvent_t sfm_ev[2] = {};
-    double sfm_call_ms = 0, sfm_kernel_ms = 0;
-    void (*free_sfm)(isv_backend *) = nullptr;
-    // isv_internal_relpose_batch (isv_relpose.hip): the same pattern
-    void *relpose_d = nullptr; size_t relpose_cap = 0;
-    hipEvent_t relpose_ev[2] = {};
-    double relpose_call_ms = 0, relpose_kernel_ms = 0;
-    void (*free_relpose)(isv_backend *) = nullptr;
+    InitSlot init_slot[ISV_INIT_STAGES];   // the batched initialisation stages' blocks, events and times (isv_init_launch.h)
     double last_ms[8] = {};
     int64_t last_counts[8] = {};
     hipGraphExec_t graph_exec = nullptr;    // ISV_GRAPH=1 (measurement hook): the captured launch chain of isv_batch_optimize

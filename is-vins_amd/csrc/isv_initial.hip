@@ -13,12 +13,10 @@
 // isv_device_math.h included, as the restatement is built with -ffp-contract=off.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <float.h>
 #include <string.h>
-#include <mutex>
 #include <vector>
-#include "isv_backend_impl.h"
+#include "isv_init_launch.h"
 #include "isv_device_math.h"
 #include "isv_initial.h"
 
@@ -502,43 +500,11 @@ int check_problem(const isv_align_problem_t *p, ProbHdr *hd) {
 
 }  // namespace
 
-namespace {
-std::mutex g_align_attr_mutex;
-
-// the handle's device block for this entry point: grow-only, freed with the handle (isv_backend_destroy calls align_free)
-void align_free(isv_backend_t *h) {
-    if (h->align_d) (void)hipFree(h->align_d);
-    for (auto &e : h->align_ev) if (e) (void)hipEventDestroy(e);
-    h->align_d = nullptr; h->align_cap = 0;
-    h->align_ev[0] = h->align_ev[1] = nullptr;
-}
-
-// the dynamic-LDS attribute is per kernel and device and process-wide: raised once per device to the largest size asked for
-hipError_t align_set_lds(int dev, size_t lds) {
-    static size_t cur[64] = {};
-    std::lock_guard<std::mutex> lk(g_align_attr_mutex);
-    if (lds <= 65536 || lds <= cur[dev & 63]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_visual_imu_align, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) cur[dev & 63] = lds;
-    return e;
-}
-}  // namespace
-
-extern "C" int isv_internal_align_last_ms(isv_backend_t *h, double out_ms[2]) {
-    if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
-    out_ms[0] = h->align_call_ms; out_ms[1] = h->align_kernel_ms;
-    return ISV_OK;
-}
+extern "C" int isv_internal_align_last_ms(isv_backend_t *h, double out_ms[2]) { return init_last_ms(h, ISV_INIT_ALIGN, out_ms); }
 
 extern "C" int isv_internal_visual_imu_align_batch(isv_backend_t *h, int32_t n, const isv_align_problem_t *const *problems, isv_align_result_t *results) {
-    const auto t_call = std::chrono::steady_clock::now();
-    if (!h) return ISV_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!problems || !results))) { h->err = "isv_internal_visual_imu_align_batch: bad arguments"; return ISV_ERR_INVALID_ARG; }
-    if (n == 0) return ISV_OK;
-    for (int i = 0; i < n; i++)
-        if (!problems[i]) { h->err = "isv_internal_visual_imu_align_batch: null problem"; return ISV_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    // one block: [headers | frames | imu rows], each section 16-byte aligned
+    InitCall call{h, ISV_INIT_ALIGN, "isv_internal_visual_imu_align_batch"};
+    if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<ProbHdr> hd(n);
     size_t n_frames = 0, n_imu = 0;
     int nf_max = 2;
@@ -556,49 +522,26 @@ extern "C" int isv_internal_visual_imu_align_batch(isv_backend_t *h, int32_t n, 
         n_frames += p->n_frames; n_imu += p->n_imu;
         if (p->n_frames > nf_max) nf_max = p->n_frames;
     }
-    if (n_frames > INT32_MAX || n_imu > INT32_MAX) { h->err = "isv_internal_visual_imu_align_batch: batch too large"; return ISV_ERR_CAPACITY; }
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_fr = al(sizeof(ProbHdr) * n), o_imu = o_fr + al(sizeof(isv_align_frame_t) * n_frames);
-    const size_t up_bytes = o_imu + sizeof(double) * 7 * (n_imu ? n_imu : 1);
-    std::vector<char> up(up_bytes);
-    memcpy(up.data(), hd.data(), sizeof(ProbHdr) * n);
+    if (n_frames > INT32_MAX || n_imu > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
+    // one upload block: [headers | frames | imu rows]; then, device only: results
+    InitLayout L;
+    const size_t o_hd = L.add(sizeof(ProbHdr) * n), o_fr = L.add(sizeof(isv_align_frame_t) * n_frames), o_imu = L.add(sizeof(double) * 7 * (n_imu ? n_imu : 1));
+    std::vector<char> up(L.end);
+    const size_t o_res = L.add(sizeof(isv_align_result_t) * n);
+    memcpy(up.data() + o_hd, hd.data(), sizeof(ProbHdr) * n);
     for (int i = 0; i < n; i++) {
         if (hd[i].status != ISV_ALIGN_OK) continue;
         const isv_align_problem_t *p = problems[i];
         memcpy(up.data() + o_fr + sizeof(isv_align_frame_t) * hd[i].frame_off, p->frames, sizeof(isv_align_frame_t) * p->n_frames);
         if (p->n_imu) memcpy(up.data() + o_imu + sizeof(double) * 7 * hd[i].imu_off, p->imu, sizeof(double) * 7 * p->n_imu);
     }
-    const size_t res_bytes = sizeof(isv_align_result_t) * n, o_res = al(up_bytes), need = o_res + res_bytes;
-    if (need > h->align_cap) {
-        if (h->align_d) (void)hipFree(h->align_d);
-        h->align_d = nullptr; h->align_cap = 0;
-        HIPCHK(h, hipMalloc(&h->align_d, need));
-        h->align_cap = need;
-        h->free_align = align_free;
-    }
-    if (!h->align_ev[0]) {
-        HIPCHK(h, hipEventCreate(&h->align_ev[0]));
-        HIPCHK(h, hipEventCreate(&h->align_ev[1]));
-        h->free_align = align_free;
-    }
-    char *d_up = (char *)h->align_d, *d_res = d_up + o_res;
     const size_t lds = lds_bytes(nf_max);
-    HIPCHK(h, align_set_lds(h->device, lds));
-    hipError_t e = hipMemcpyAsync(d_up, up.data(), up_bytes, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_res, 0, res_bytes, h->stream);
-    if (e == hipSuccess) e = hipEventRecord(h->align_ev[0], h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_visual_imu_align, dim3(n), dim3(kLanes), lds, h->stream, (const ProbHdr *)d_up, (const isv_align_frame_t *)(d_up + o_fr),
-                           (const double *)(d_up + o_imu), (isv_align_result_t *)d_res, nf_max);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->align_ev[1], h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d_res, res_bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    float kms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&kms, h->align_ev[0], h->align_ev[1]);
-    if (e != hipSuccess) { h->err = std::string("isv_internal_visual_imu_align_batch: ") + hipGetErrorString(e); return ISV_ERR_DEVICE; }
-    h->align_kernel_ms = kms;
-    h->align_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return ISV_OK;
+    HIPCHK(h, isv_raise_dynamic_lds((const void *)k_visual_imu_align, h->device, lds));
+    return call.run(
+        up, L.end, L.end,
+        [&](char *d) {
+            hipLaunchKernelGGL(k_visual_imu_align, dim3(n), dim3(kLanes), lds, h->stream, (const ProbHdr *)(d + o_hd), (const isv_align_frame_t *)(d + o_fr),
+                               (const double *)(d + o_imu), (isv_align_result_t *)(d + o_res), nf_max);
+        },
+        {{results, o_res, sizeof(isv_align_result_t) * n}}, [] {});
 }

@@ -88,6 +88,8 @@ enum { ISV_CNT_LINEARIZE, ISV_CNT_SOLVE, ISV_CNT_ELIM, ISV_CNT_WINDOW_ITERS, ISV
 // memory go through the runtime's own staging and may complete lazily, which stalled the NEXT upload by 13-30 ms for
 // batches above ~1 MB of records
 struct SolverStage { SolveState *st; double *tc, *tr, *ts; int32_t *ta; isv_marg_result_t *marg; };
+// raise fn's dynamic-LDS attribute on `device` (the current one) to lds bytes unless it already allows that (isv_solver.hip)
+hipError_t isv_raise_dynamic_lds(const void *fn, int device, size_t lds);
 // isv_batch_upload's device half (isv_sequence.hip): raw CSR -> lm_* / f_* / pg_* arrays
 size_t upload_build_lds_bytes(int N, int lcap);
 int isv_upload_build_enqueue(DevBatch &d, const int32_t *optr, const double *obs_raw, int lcap, hipStream_t st);

@@ -13,10 +13,9 @@
 // contraction is off for the whole translation unit.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <string.h>
 #include <vector>
-#include "isv_backend_impl.h"
+#include "isv_init_launch.h"
 #include "isv_relpose.h"
 #include "isv_init_common.h"
 
@@ -225,30 +224,14 @@ int map_status(int sfm_status) {
                                                                                               : ISV_RELPOSE_REFUSED_INPUT;
 }
 
-void relpose_free(isv_backend_t *h) {
-    if (h->relpose_d) (void)hipFree(h->relpose_d);
-    for (auto &e : h->relpose_ev) if (e) (void)hipEventDestroy(e);
-    h->relpose_d = nullptr; h->relpose_cap = 0;
-    h->relpose_ev[0] = h->relpose_ev[1] = nullptr;
-}
-
 }  // namespace
 
-extern "C" int isv_internal_relpose_last_ms(isv_backend_t *h, double out_ms[2]) {
-    if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
-    out_ms[0] = h->relpose_call_ms; out_ms[1] = h->relpose_kernel_ms;
-    return ISV_OK;
-}
+extern "C" int isv_internal_relpose_last_ms(isv_backend_t *h, double out_ms[2]) { return init_last_ms(h, ISV_INIT_RELPOSE, out_ms); }
 
 extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv_sfm_problem_t *const *problems, isv_relpose_result_t *results,
                                           int32_t *const *masks) {
-    const auto t_call = std::chrono::steady_clock::now();
-    if (!h) return ISV_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!problems || !results))) { h->err = "isv_internal_relpose_batch: bad arguments"; return ISV_ERR_INVALID_ARG; }
-    if (n == 0) return ISV_OK;
-    for (int i = 0; i < n; i++)
-        if (!problems[i]) { h->err = "isv_internal_relpose_batch: null problem"; return ISV_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
+    InitCall call{h, ISV_INIT_RELPOSE, "isv_internal_relpose_batch"};
+    if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<RpHdr> hd(n);
     size_t n_tr = 0, n_obs = 0, n_fr = 0;
     for (int i = 0; i < n; i++) {
@@ -261,14 +244,14 @@ extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv
         H.trk_off = (int32_t)n_tr; H.obs_off = (int32_t)n_obs; H.frame_off = (int32_t)n_fr;
         n_tr += p->n_tracks; n_obs += p->n_obs; n_fr += p->n_frames;
     }
-    if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_fr > INT32_MAX) { h->err = "isv_internal_relpose_batch: batch too large"; return ISV_ERR_CAPACITY; }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // one upload block: [headers | tracks | obs | dv | sdt]; then, device only: results, per-track masks
-    const size_t o_tr = al(sizeof(RpHdr) * n), o_obs = o_tr + al(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_dv = o_obs + al(16 * (n_obs + 1));
-    const size_t o_sdt = o_dv + al(24 * (n_fr + 1)), up_bytes = o_sdt + al(8 * (n_fr + 1));
-    const size_t o_res = up_bytes, o_mask = o_res + al(sizeof(isv_relpose_result_t) * n), need = o_mask + 4 * (n_tr + 1);
-    std::vector<char> up(up_bytes);
-    memcpy(up.data(), hd.data(), sizeof(RpHdr) * n);
+    if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_fr > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
+    // one upload block: [headers | tracks | obs | dv | sdt]; then, device only: results (zeroed before the launch), per-track masks
+    InitLayout L;
+    const size_t o_hd = L.add(sizeof(RpHdr) * n), o_tr = L.add(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_obs = L.add(16 * (n_obs + 1));
+    const size_t o_dv = L.add(24 * (n_fr + 1)), o_sdt = L.add(8 * (n_fr + 1));
+    std::vector<char> up(L.end);
+    const size_t o_res = L.add(sizeof(isv_relpose_result_t) * n), o_mask = L.add(4 * (n_tr + 1));
+    memcpy(up.data() + o_hd, hd.data(), sizeof(RpHdr) * n);
     for (int i = 0; i < n; i++) {
         const RpHdr &H = hd[i];
         if (H.status != ISV_RELPOSE_OK) continue;
@@ -278,43 +261,21 @@ extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv
         memcpy(up.data() + o_dv + 24 * (size_t)H.frame_off, p->delta_v, 24 * (size_t)H.nf);
         memcpy(up.data() + o_sdt + 8 * (size_t)H.frame_off, p->sum_dt, 8 * (size_t)H.nf);
     }
-    if (need > h->relpose_cap) {
-        if (h->relpose_d) (void)hipFree(h->relpose_d);
-        h->relpose_d = nullptr; h->relpose_cap = 0;
-        HIPCHK(h, hipMalloc(&h->relpose_d, need));
-        h->relpose_cap = need;
-        h->free_relpose = relpose_free;
-    }
-    if (!h->relpose_ev[0]) {
-        HIPCHK(h, hipEventCreate(&h->relpose_ev[0]));
-        HIPCHK(h, hipEventCreate(&h->relpose_ev[1]));
-        h->free_relpose = relpose_free;
-    }
-    char *d = (char *)h->relpose_d;
     std::vector<int32_t> mk(n_tr + 1);
-    hipError_t e = hipMemcpyAsync(d, up.data(), up_bytes, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_res, 0, o_mask - o_res, h->stream);   // the fields a refusal leaves unwritten
-    if (e == hipSuccess) e = hipEventRecord(h->relpose_ev[0], h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_relpose, dim3(n), dim3(kLanes), 0, h->stream, (const RpHdr *)d, (const isv_sfm_track_t *)(d + o_tr),
-                           (const double *)(d + o_obs), (const double *)(d + o_dv), (const double *)(d + o_sdt),
-                           (isv_relpose_result_t *)(d + o_res), (int32_t *)(d + o_mask));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->relpose_ev[1], h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(isv_relpose_result_t) * n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && masks) e = hipMemcpyAsync(mk.data(), d + o_mask, 4 * n_tr, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    float kms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&kms, h->relpose_ev[0], h->relpose_ev[1]);
-    if (e != hipSuccess) { h->err = std::string("isv_internal_relpose_batch: ") + hipGetErrorString(e); return ISV_ERR_DEVICE; }
-    if (masks)
-        for (int i = 0; i < n; i++) {
-            if (!masks[i]) continue;
-            const RpHdr &H = hd[i];
-            if (H.status == ISV_RELPOSE_OK) memcpy(masks[i], mk.data() + H.trk_off, 4 * (size_t)H.ntr);   // (a refused input's n_tracks is not trusted)
-        }
-    h->relpose_kernel_ms = kms;
-    h->relpose_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return ISV_OK;
+    return call.run(
+        up, o_mask, L.end,
+        [&](char *d) {
+            hipLaunchKernelGGL(k_relpose, dim3(n), dim3(kLanes), 0, h->stream, (const RpHdr *)(d + o_hd), (const isv_sfm_track_t *)(d + o_tr),
+                               (const double *)(d + o_obs), (const double *)(d + o_dv), (const double *)(d + o_sdt),
+                               (isv_relpose_result_t *)(d + o_res), (int32_t *)(d + o_mask));
+        },
+        {{results, o_res, sizeof(isv_relpose_result_t) * n}, {masks ? mk.data() : nullptr, o_mask, 4 * n_tr}},
+        [&] {
+            if (masks)
+                for (int i = 0; i < n; i++) {
+                    if (!masks[i]) continue;
+                    const RpHdr &H = hd[i];
+                    if (H.status == ISV_RELPOSE_OK) memcpy(masks[i], mk.data() + H.trk_off, 4 * (size_t)H.ntr);   // (a refused input's n_tracks is not trusted)
+                }
+        });
 }

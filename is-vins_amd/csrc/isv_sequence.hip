@@ -21,7 +21,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include "isv_backend_impl.h"
 
 #define ISV_SEQ_RING 32                 // observation ring of a track (>= ISV_MAX_FRAMES, power of two)
@@ -539,12 +538,9 @@ __global__ __launch_bounds__(256) void k_upload_build(DevBatch d, const int32_t 
 size_t upload_build_lds_bytes(int N, int lcap) { return ((size_t)2 * lcap + 9 * ((size_t)N * (N - 1) / 2 + 1)) * sizeof(int32_t); }
 int isv_upload_build_enqueue(DevBatch &d, const int32_t *optr, const double *obs_raw, int lcap, hipStream_t st) {
     const size_t lds = upload_build_lds_bytes(d.Nr, lcap);
-    if (lds > 48 * 1024) {
-        static std::mutex mtx; static size_t cur[64] = {};
-        int dev = 0; (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lk(mtx);
-        if (lds > cur[dev & 63]) { if (hipFuncSetAttribute((const void *)k_upload_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return ISV_ERR_DEVICE; cur[dev & 63] = lds; }
-    }
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (isv_raise_dynamic_lds((const void *)k_upload_build, dev, lds) != hipSuccess) return ISV_ERR_DEVICE;
     hipLaunchKernelGGL(k_upload_build, dim3(d.B), dim3(256), lds, st, d, optr, obs_raw, lcap);
     return hipGetLastError() == hipSuccess ? ISV_OK : ISV_ERR_DEVICE;
 }

@@ -15,13 +15,11 @@
 // tests/native/isv_sfm_oracle.c operation by operation.  No atomics.  Contraction is off for the whole translation unit.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <float.h>
 #include <string.h>
-#include <mutex>
 #include <unordered_map>
 #include <vector>
-#include "isv_backend_impl.h"
+#include "isv_init_launch.h"
 #include "isv_sfm.h"
 #include "isv_init_common.h"
 
@@ -995,41 +993,11 @@ int isv_sfm_check_problem(const isv_sfm_problem_t *p, bool with_l) {
     return ISV_SFM_OK;
 }
 
-namespace {
-
-std::mutex g_sfm_attr_mutex;
-
-void sfm_free(isv_backend_t *h) {
-    if (h->sfm_d) (void)hipFree(h->sfm_d);
-    for (auto &e : h->sfm_ev) if (e) (void)hipEventDestroy(e);
-    h->sfm_d = nullptr; h->sfm_cap = 0;
-    h->sfm_ev[0] = h->sfm_ev[1] = nullptr;
-}
-
-hipError_t sfm_set_lds(int dev, size_t lds) {
-    static size_t cur[64] = {};
-    std::lock_guard<std::mutex> lk(g_sfm_attr_mutex);
-    if (lds <= 65536 || lds <= cur[dev & 63]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_sfm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) cur[dev & 63] = lds;
-    return e;
-}
-}  // namespace
-
-extern "C" int isv_internal_sfm_last_ms(isv_backend_t *h, double out_ms[2]) {
-    if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
-    out_ms[0] = h->sfm_call_ms; out_ms[1] = h->sfm_kernel_ms;
-    return ISV_OK;
-}
+extern "C" int isv_internal_sfm_last_ms(isv_backend_t *h, double out_ms[2]) { return init_last_ms(h, ISV_INIT_SFM, out_ms); }
 
 extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm_problem_t *const *problems, isv_sfm_result_t *results) {
-    const auto t_call = std::chrono::steady_clock::now();
-    if (!h) return ISV_ERR_INVALID_ARG;
-    if (n < 0 || (n > 0 && (!problems || !results))) { h->err = "isv_internal_sfm_batch: bad arguments"; return ISV_ERR_INVALID_ARG; }
-    if (n == 0) return ISV_OK;
-    for (int i = 0; i < n; i++)
-        if (!problems[i]) { h->err = "isv_internal_sfm_batch: null problem"; return ISV_ERR_INVALID_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
+    InitCall call{h, ISV_INIT_SFM, "isv_internal_sfm_batch"};
+    if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<SfmHdr> hd(n);
     size_t n_tr = 0, n_obs = 0, n_poff = 0, n_pts = 0, n_fr = 0;
     int nt_max = 1, no_max = 1, nw_max = 2;
@@ -1048,15 +1016,17 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
         n_tr += p->n_tracks; n_obs += p->n_obs; n_poff += p->n_frames + 1; n_pts += p->n_pts; n_fr += p->n_frames;
         nt_max = std::max(nt_max, (int)p->n_tracks); no_max = std::max(no_max, (int)p->n_obs); nw_max = std::max(nw_max, (int)p->n_window);
     }
-    if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_pts > INT32_MAX || n_poff > INT32_MAX) { h->err = "isv_internal_sfm_batch: batch too large"; return ISV_ERR_CAPACITY; }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_pts > INT32_MAX || n_poff > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
     // one upload block: [headers | tracks | obs | dv | sdt | pt_uv | pt_off | pt_trk]; then, device only: results, positions,
-    // states, the per-track blocks
-    const size_t o_tr = al(sizeof(SfmHdr) * n), o_obs = o_tr + al(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_dv = o_obs + al(16 * (n_obs + 1));
-    const size_t o_sdt = o_dv + al(24 * (n_fr + 1)), o_uv = o_sdt + al(8 * (n_fr + 1)), o_poff = o_uv + al(16 * (n_pts + 1));
-    const size_t o_ptrk = o_poff + al(4 * (n_poff + 1)), up_bytes = o_ptrk + al(4 * (n_pts + 1));
-    std::vector<char> up(up_bytes);
-    memcpy(up.data(), hd.data(), sizeof(SfmHdr) * n);
+    // states (the three zeroed before the launch), the per-track blocks
+    InitLayout L;
+    const size_t o_hd = L.add(sizeof(SfmHdr) * n), o_tr = L.add(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_obs = L.add(16 * (n_obs + 1));
+    const size_t o_dv = L.add(24 * (n_fr + 1)), o_sdt = L.add(8 * (n_fr + 1)), o_uv = L.add(16 * (n_pts + 1)), o_poff = L.add(4 * (n_poff + 1));
+    const size_t o_ptrk = L.add(4 * (n_pts + 1));
+    std::vector<char> up(L.end);
+    const size_t o_res = L.add(sizeof(isv_sfm_result_t) * n), o_pos = L.add(24 * (n_tr + 1)), o_st = L.add(4 * (n_tr + 1));
+    const size_t o_scr = L.add(sizeof(double) * kScr * (n_tr + 1));
+    memcpy(up.data() + o_hd, hd.data(), sizeof(SfmHdr) * n);
     std::unordered_map<int32_t, int32_t> last_of;
     for (int i = 0; i < n; i++) {
         const SfmHdr &H = hd[i];
@@ -1079,51 +1049,26 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
     }
     const int nc_max = 6 * nw_max - 9;
     const int nS = std::max(nc_max * (nc_max + 1) / 2, kLanes * 14);
-    const size_t o_res = al(up_bytes), o_pos = o_res + al(sizeof(isv_sfm_result_t) * n), o_st = o_pos + al(24 * (n_tr + 1));
-    const size_t o_scr = o_st + al(4 * (n_tr + 1)), need = o_scr + sizeof(double) * kScr * (n_tr + 1);
-    if (need > h->sfm_cap) {
-        if (h->sfm_d) (void)hipFree(h->sfm_d);
-        h->sfm_d = nullptr; h->sfm_cap = 0;
-        HIPCHK(h, hipMalloc(&h->sfm_d, need));
-        h->sfm_cap = need;
-        h->free_sfm = sfm_free;
-    }
-    if (!h->sfm_ev[0]) {
-        HIPCHK(h, hipEventCreate(&h->sfm_ev[0]));
-        HIPCHK(h, hipEventCreate(&h->sfm_ev[1]));
-        h->free_sfm = sfm_free;
-    }
-    char *d = (char *)h->sfm_d;
     const size_t lds = lds_bytes(nt_max, no_max, nS);
-    HIPCHK(h, sfm_set_lds(h->device, lds));
+    HIPCHK(h, isv_raise_dynamic_lds((const void *)k_sfm, h->device, lds));
     std::vector<double> pos(3 * (n_tr + 1));
     std::vector<int32_t> st(n_tr + 1);
-    hipError_t e = hipMemcpyAsync(d, up.data(), up_bytes, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_res, 0, o_scr - o_res, h->stream);
-    if (e == hipSuccess) e = hipEventRecord(h->sfm_ev[0], h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sfm, dim3(n), dim3(kLanes), lds, h->stream, (const SfmHdr *)d, (const isv_sfm_track_t *)(d + o_tr), (const double *)(d + o_obs),
-                           (const int32_t *)(d + o_poff), (const int32_t *)(d + o_ptrk), (const double *)(d + o_uv), (const double *)(d + o_dv),
-                           (const double *)(d + o_sdt), (double *)(d + o_scr), (isv_sfm_result_t *)(d + o_res), (double *)(d + o_pos),
-                           (int32_t *)(d + o_st), nt_max, no_max, nS);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->sfm_ev[1], h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(isv_sfm_result_t) * n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pos.data(), d + o_pos, 24 * n_tr, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d + o_st, 4 * n_tr, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    float kms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&kms, h->sfm_ev[0], h->sfm_ev[1]);
-    if (e != hipSuccess) { h->err = std::string("isv_internal_sfm_batch: ") + hipGetErrorString(e); return ISV_ERR_DEVICE; }
-    for (int i = 0; i < n; i++) {   // per-track outputs of the problems that reached the BA
-        const SfmHdr &H = hd[i];
-        const int s = results[i].status;
-        if (H.status != ISV_SFM_OK || !(s == ISV_SFM_OK || s == ISV_SFM_REFUSED_BA_NOT_CONVERGED || s == ISV_SFM_REFUSED_ALL_PNP_POINTS)) continue;
-        memcpy(problems[i]->position, pos.data() + 3 * (size_t)H.trk_off, 24 * (size_t)H.ntr);
-        memcpy(problems[i]->state, st.data() + H.trk_off, 4 * (size_t)H.ntr);
-    }
-    h->sfm_kernel_ms = kms;
-    h->sfm_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return ISV_OK;
+    return call.run(
+        up, o_scr, L.end,
+        [&](char *d) {
+            hipLaunchKernelGGL(k_sfm, dim3(n), dim3(kLanes), lds, h->stream, (const SfmHdr *)(d + o_hd), (const isv_sfm_track_t *)(d + o_tr),
+                               (const double *)(d + o_obs), (const int32_t *)(d + o_poff), (const int32_t *)(d + o_ptrk), (const double *)(d + o_uv),
+                               (const double *)(d + o_dv), (const double *)(d + o_sdt), (double *)(d + o_scr), (isv_sfm_result_t *)(d + o_res),
+                               (double *)(d + o_pos), (int32_t *)(d + o_st), nt_max, no_max, nS);
+        },
+        {{results, o_res, sizeof(isv_sfm_result_t) * n}, {pos.data(), o_pos, 24 * n_tr}, {st.data(), o_st, 4 * n_tr}},
+        [&] {
+            for (int i = 0; i < n; i++) {   // per-track outputs of the problems that reached the BA
+                const SfmHdr &H = hd[i];
+                const int s = results[i].status;
+                if (H.status != ISV_SFM_OK || !(s == ISV_SFM_OK || s == ISV_SFM_REFUSED_BA_NOT_CONVERGED || s == ISV_SFM_REFUSED_ALL_PNP_POINTS)) continue;
+                memcpy(problems[i]->position, pos.data() + 3 * (size_t)H.trk_off, 24 * (size_t)H.ntr);
+                memcpy(problems[i]->state, st.data() + H.trk_off, 4 * (size_t)H.ntr);
+            }
+        });
 }

@@ -239,7 +239,18 @@ static int dal(T **p, size_t n, std::vector<void *> &allocs, std::string &err) {
     return ISV_OK;
 }
 #define TRYA(x) do { int rc_ = (x); if (rc_ != ISV_OK) return rc_; } while (0)
-static std::mutex g_lds_attr_mutex;
+// the dynamic-LDS attribute is per kernel and device and process-wide: raised to the largest size asked for and never lowered,
+// so that handles of different shapes and the entry points sharing a kernel do not lower each other's value
+hipError_t isv_raise_dynamic_lds(const void *fn, int device, size_t lds) {
+    static std::mutex mtx;
+    static std::map<std::pair<const void *, int>, size_t> raised;
+    std::lock_guard<std::mutex> lk(mtx);
+    size_t &cur = raised[{fn, device}];
+    if (lds <= cur) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) cur = lds;
+    return e;
+}
 // dynamic LDS of k_dogleg (candidate-point IMU / prior evaluation on the LDS path + the two tangent vectors) and of the step control
 static size_t dogleg_lds_bytes(const DevBatch &d) {
     // + two 496-double staging rows for the IMU J^T J records of the model pieces and the tangent step (np)
@@ -406,16 +417,7 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
             }
         }
     }
-    // the dynamic-LDS attribute is per kernel and device and process-wide: handles of different shapes must not lower each other's value
-    {
-        static std::map<std::pair<const void *, int>, size_t> raised;
-        std::lock_guard<std::mutex> lk(g_lds_attr_mutex);
-        for (const SolverKernel &e : hc.kern) {
-            if (!e.lds) continue;
-            size_t &cur = raised[{e.fn, dev0_}];
-            if (e.lds > cur) { HCHK(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds)); cur = e.lds; }
-        }
-    }
+    for (const SolverKernel &e : hc.kern) HCHK(isv_raise_dynamic_lds(e.fn, dev0_, e.lds));
     // device figures the per-launch variant choice needs (once per handle, not per isv_batch_optimize): hc.n_cus (above) and the
     // workgroups of k_dogleg<true, EX> per CU by registers alone (a small dynamic LDS request); the LDS bound is applied per enqueue
     {

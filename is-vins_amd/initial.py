@@ -66,34 +66,53 @@ class Problem:
 
 
 def _bind(lib):
-    if getattr(lib, "_align_bound", False):
+    """argument types of the batched initialisation stages' internal entry points and their *_last_ms readers (the SfM and
+    relative-pose structs are defined further down)"""
+    if getattr(lib, "_init_bound", False):
         return
-    lib.isv_internal_visual_imu_align_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(isv_align_problem_t)), C.POINTER(isv_align_result_t)]
-    lib.isv_internal_visual_imu_align_batch.restype = C.c_int
-    lib.isv_internal_align_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.isv_internal_align_last_ms.restype = C.c_int
-    lib._align_bound = True
+    pp = lambda t: C.POINTER(C.POINTER(t))
+    for name, args in (("isv_internal_visual_imu_align_batch", [pp(isv_align_problem_t), C.POINTER(isv_align_result_t)]),
+                       ("isv_internal_sfm_batch", [pp(isv_sfm_problem_t), C.POINTER(isv_sfm_result_t)]),
+                       ("isv_internal_relpose_batch", [pp(isv_sfm_problem_t), C.POINTER(isv_relpose_result_t), pp(C.c_int32)])):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_int32] + args
+        getattr(lib, name).restype = C.c_int
+    for stage in ("align", "sfm", "relpose"):
+        getattr(lib, f"isv_internal_{stage}_last_ms").argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        getattr(lib, f"isv_internal_{stage}_last_ms").restype = C.c_int
+    lib._init_bound = True
+
+
+_bind_sfm = _bind_relpose = _bind   # the names the SfM and relative-pose tests bind through
+
+
+def _run(be, entry, problem_t, result_t, problems, *extra):
+    """one call of a batched stage's entry point on the backend handle `be`; returns the list of results"""
+    _bind(be.lib)
+    n = len(problems)
+    ptrs = (C.POINTER(problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
+    res = (result_t * max(n, 1))()
+    rc = getattr(be.lib, entry)(be.h, n, ptrs, res, *extra)
+    if rc != 0:
+        raise backend.BackendError(f"{entry}: {backend.STATUS.get(rc, rc)}: {be.lib.isv_backend_last_error(be.h)}")
+    return [res[i] for i in range(n)]
+
+
+def _last_ms(be, stage):
+    """(whole call, kernel) milliseconds of the stage's last call on this handle"""
+    _bind(be.lib)
+    out = (C.c_double * 2)()
+    getattr(be.lib, f"isv_internal_{stage}_last_ms")(be.h, out)
+    return out[0], out[1]
 
 
 def align_batch(be, problems):
     """isv_internal_visual_imu_align_batch on the backend handle `be` (backend.Backend); returns the list of results"""
-    lib = be.lib
-    _bind(lib)
-    n = len(problems)
-    ptrs = (C.POINTER(isv_align_problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
-    res = (isv_align_result_t * max(n, 1))()
-    rc = lib.isv_internal_visual_imu_align_batch(be.h, n, ptrs, res)
-    if rc != 0:
-        raise backend.BackendError(f"isv_internal_visual_imu_align_batch: {backend.STATUS.get(rc, rc)}: {lib.isv_backend_last_error(be.h)}")
-    return [res[i] for i in range(n)]
+    return _run(be, "isv_internal_visual_imu_align_batch", isv_align_problem_t, isv_align_result_t, problems)
 
 
 def last_ms(be):
     """(whole call, kernel) milliseconds of the last align_batch on this handle"""
-    _bind(be.lib)
-    out = (C.c_double * 2)()
-    be.lib.isv_internal_align_last_ms(be.h, out)
-    return out[0], out[1]
+    return _last_ms(be, "align")
 
 
 def make_problem(seed=0, n_frames=11, window_frame=None, cam_dt=0.1, imu_per_frame=10, radius=1.0, speed=1.0, sfm_scale=0.37,
@@ -263,36 +282,15 @@ class SfmProblem:
         self.truth = {}
 
 
-def _bind_sfm(lib):
-    if getattr(lib, "_sfm_bound", False):
-        return
-    lib.isv_internal_sfm_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(isv_sfm_problem_t)), C.POINTER(isv_sfm_result_t)]
-    lib.isv_internal_sfm_batch.restype = C.c_int
-    lib.isv_internal_sfm_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.isv_internal_sfm_last_ms.restype = C.c_int
-    lib._sfm_bound = True
-
-
 def sfm_batch(be, problems):
     """isv_internal_sfm_batch on the backend handle `be`; returns the results (each problem's position / state arrays are
     filled in place)"""
-    lib = be.lib
-    _bind_sfm(lib)
-    n = len(problems)
-    ptrs = (C.POINTER(isv_sfm_problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
-    res = (isv_sfm_result_t * max(n, 1))()
-    rc = lib.isv_internal_sfm_batch(be.h, n, ptrs, res)
-    if rc != 0:
-        raise backend.BackendError(f"isv_internal_sfm_batch: {backend.STATUS.get(rc, rc)}: {lib.isv_backend_last_error(be.h)}")
-    return [res[i] for i in range(n)]
+    return _run(be, "isv_internal_sfm_batch", isv_sfm_problem_t, isv_sfm_result_t, problems)
 
 
 def sfm_last_ms(be):
     """(whole call, kernel) milliseconds of the last sfm_batch on this handle"""
-    _bind_sfm(be.lib)
-    out = (C.c_double * 2)()
-    be.lib.isv_internal_sfm_last_ms(be.h, out)
-    return out[0], out[1]
+    return _last_ms(be, "sfm")
 
 
 def copy_sfm_to_align(res, align_problem):
@@ -466,17 +464,6 @@ class isv_relpose_result_t(C.Structure):
         return np.ctypeslib.as_array(getattr(self, name)).copy()
 
 
-def _bind_relpose(lib):
-    if getattr(lib, "_relpose_bound", False):
-        return
-    lib.isv_internal_relpose_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(isv_sfm_problem_t)),
-                                               C.POINTER(isv_relpose_result_t), C.POINTER(C.POINTER(C.c_int32))]
-    lib.isv_internal_relpose_batch.restype = C.c_int
-    lib.isv_internal_relpose_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.isv_internal_relpose_last_ms.restype = C.c_int
-    lib._relpose_bound = True
-
-
 def apply_relpose(res, sp):
     """relativePose's outputs (l, relative_R, relative_T) of an OK result into the SfM problem it was computed from"""
     sp.c.l = res.l
@@ -488,19 +475,11 @@ def relpose_batch(be, problems, write=False, masks=False):
     """isv_internal_relpose_batch on the backend handle `be`; returns the results, and with masks=True also a list of
     per-track inlier masks (int32 [n_tracks]: 1 / 0 for the chosen pair's correspondences, -1 elsewhere).  write=True copies
     l / relative_R / relative_T of every OK result into its problem (apply_relpose)."""
-    lib = be.lib
-    _bind_relpose(lib)
-    n = len(problems)
-    ptrs = (C.POINTER(isv_sfm_problem_t) * max(n, 1))(*[C.pointer(p.c) for p in problems])
-    res = (isv_relpose_result_t * max(n, 1))()
     mk, mptr = None, None
     if masks:
         mk = [np.full(max(p.c.n_tracks, 1), -1, dtype=np.int32) for p in problems]
-        mptr = (C.POINTER(C.c_int32) * max(n, 1))(*[m.ctypes.data_as(C.POINTER(C.c_int32)) for m in mk])
-    rc = lib.isv_internal_relpose_batch(be.h, n, ptrs, res, mptr)
-    if rc != 0:
-        raise backend.BackendError(f"isv_internal_relpose_batch: {backend.STATUS.get(rc, rc)}: {lib.isv_backend_last_error(be.h)}")
-    out = [res[i] for i in range(n)]
+        mptr = (C.POINTER(C.c_int32) * max(len(problems), 1))(*[m.ctypes.data_as(C.POINTER(C.c_int32)) for m in mk])
+    out = _run(be, "isv_internal_relpose_batch", isv_sfm_problem_t, isv_relpose_result_t, problems, mptr)
     if write:
         for r, p in zip(out, problems):
             if r.status == 0:
@@ -510,10 +489,7 @@ def relpose_batch(be, problems, write=False, masks=False):
 
 def relpose_last_ms(be):
     """(whole call, kernel) milliseconds of the last relpose_batch on this handle"""
-    _bind_relpose(be.lib)
-    out = (C.c_double * 2)()
-    be.lib.isv_internal_relpose_last_ms(be.h, out)
-    return out[0], out[1]
+    return _last_ms(be, "relpose")
 
 
 def initial_structure_from_tracks_batch(be, sfm_problems, align_problems):
