@@ -16,7 +16,7 @@
 #include "isv_device_types.h"
 #include "isv_kernels.h"
 
-#include "isv_backend_impl.h"
+#include "isv_batch_buffers.h"
 
 extern "C" int isv_abi_version(void) { return ISV_ABI_VERSION; }
 
@@ -43,6 +43,8 @@ extern "C" void isv_backend_destroy(isv_backend_t *h) {
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
+
+template <typename T> static void point_at(T *&p, char *at) { p = (T *)at; }
 
 static int create_impl(isv_backend *h) {
     const isv_config_t &c = h->cfg;
@@ -75,109 +77,62 @@ static int create_impl(isv_backend *h) {
     d.alpha_cut = c.alpha;
     d.init_depth = c.init_depth;
     const size_t NI = B * (N - 1);
-    TRY(dalloc(h, &d.Ps, B * N * 3)); TRY(dalloc(h, &d.Rs, B * N * 9)); TRY(dalloc(h, &d.Vs, B * N * 3));
-    TRY(dalloc(h, &d.Bas, B * N * 3)); TRY(dalloc(h, &d.Bgs, B * N * 3)); TRY(dalloc(h, &d.tic, B * 3)); TRY(dalloc(h, &d.ric, B * 9));
-    TRY(dalloc(h, &d.depth, L)); TRY(dalloc(h, &d.solve_flag, L));
-    TRY(dalloc(h, &d.pose, B * N * 7)); TRY(dalloc(h, &d.sb, B * N * 9)); TRY(dalloc(h, &d.ex, B * 7)); TRY(dalloc(h, &d.lam, L));
+    // the transfer buffers (isv_batch_buffers.h).  Everything a RAW upload sends lives in ONE pinned block and ONE device block with
+    // the same layout, so that an upload is ONE host-to-device copy: on this GPU a copy command costs 20-50 us of stream time whatever
+    // its size (rocprofv3: 30 commands per upload, 0.7 ms of transfers inside 1.5 ms of stream time).  The solver's outputs: one pinned
+    // and one device block as well (a download was 24 copy commands: ~0.8 of its 1.7 ms).  Pass 0 lays the blocks out, pass 1 points
+    // the buffers into them and allocates the ones outside (the derived arrays, the pristine twins).
+    const BatchDims cap{B, L, F, F, T};
+    char *hb[2] = {}, *db[2] = {};             // [0] the upload block, [1] the output block
+    for (int pass = 0;; pass++) {
+        BlockLayout lay[2];
+        int rc = ISV_OK;
+        bool back = false;
+        for_each_batch_buffer(h, cap, [&](unsigned role, const char *, auto *&hp, auto *&dp, size_t cnt) {
+            const size_t bytes = sizeof(*hp) * cnt;
+            if (role & BUF_DERIVED) {
+                if (pass && rc == ISV_OK) rc = dalloc(h, &dp, cnt);
+                if (pass && rc == ISV_OK) rc = halloc(h, &hp, cnt);
+                return;
+            }
+            const int k = (role & BUF_OUT) ? 1 : 0, tw = buf_twin(role);
+            const size_t off = lay[k].add(bytes);
+            if (pass) {
+                point_at(hp, hb[k] + off); point_at(dp, db[k] + off);
+                char *twin = nullptr;
+                if (tw >= 0 && rc == ISV_OK && (rc = dalloc(h, &twin, bytes)) == ISV_OK) h->pristine[tw] = twin;
+                return;
+            }
+            if ((role & BUF_UP2) && !h->split_bytes) h->split_bytes = off;           // (where the two-part upload cuts)
+            if (role & BUF_BACK) { if (!back) h->down_a_off = off; back = true; h->down_a_bytes = off + bytes - h->down_a_off; }
+        });
+        TRY(rc);
+        if (pass) break;
+        for (int k = 0; k < 2; k++) {
+            const size_t tot = lay[k].end ? lay[k].end : 1;
+            TRY(halloc(h, &hb[k], tot)); TRY(dalloc(h, &db[k], tot));
+            HIPCHK(h, hipMemset(db[k], 0, tot)); memset(hb[k], 0, tot);
+        }
+        h->arena_h = hb[0]; h->arena_d = db[0]; h->arena_bytes = lay[0].end;
+        h->down_h = hb[1]; h->down_d = db[1]; h->down_bytes = lay[1].end;
+    }
+    h->stage.st = h->h.st;      // (the solver's staging of the solve states: the same record)
+    h->dev_build = getenv("ISV_HOST_PACK") == nullptr && upload_build_lds_bytes(c.n_frames, c.max_landmarks > 1 ? c.max_landmarks : 1) <= 64 * 1024;
     TRY(dalloc(h, &d.cpose, B * N * 7)); TRY(dalloc(h, &d.csb, B * N * 9)); TRY(dalloc(h, &d.clam, L));
-    TRY(dalloc(h, &d.lm_off, B + 1)); TRY(dalloc(h, &d.f_off, B + 1));
-    TRY(dalloc(h, &d.lm_host, L)); TRY(dalloc(h, &d.lm_k, L)); TRY(dalloc(h, &d.lm_f0, L)); TRY(dalloc(h, &d.lm_pts_i, L * 3));
-    TRY(dalloc(h, &d.f_rec, F)); TRY(dalloc(h, &d.f_pts_j, F * 2)); TRY(dalloc(h, &d.f_pts_z, F));
-    TRY(dalloc(h, &d.tile_win, T)); TRY(dalloc(h, &d.tile_f0, T)); TRY(dalloc(h, &d.tile_n, T));
-    TRY(dalloc(h, &d.pg_perm, F)); TRY(dalloc(h, &d.pg_off, B * ((size_t)c.n_frames * (c.n_frames - 1) / 2 + 1)));
-    TRY(dalloc(h, &d.pg_sched, B * ((size_t)c.n_frames * (c.n_frames - 1) / 2))); TRY(dalloc(h, &d.pg_sched_off, B * (ISV_SWEEP_WAVES + 1)));
-    TRY(dalloc(h, &d.pg_rec, F * 2)); TRY(dalloc(h, &d.pg_pts, F * 2)); TRY(dalloc(h, &d.flm, F * 8)); TRY(dalloc(h, &d.pg_wstart, B * (ISV_SWEEP_WAVES + 1)));
+    TRY(dalloc(h, &d.flm, F * 8));
     // d.fused_visual (k_lin_gram, or the unfused k_proj_linearize<0> + k_sweep_mfma pair) is decided per UPLOAD from the
     // windows that were handed over, not from the handle's capacity: see isv_batch_upload
     d.fused_visual = 1;
-    TRY(dalloc(h, &d.imu_in, NI * ISV_IMU_IN)); TRY(dalloc(h, &d.imu_cov, NI * 225)); TRY(dalloc(h, &d.imu_sqrt, NI * 225));
-    TRY(dalloc(h, &d.imu_skip, NI));
-    TRY(dalloc(h, &d.se3, B)); TRY(dalloc(h, &d.lin9, B)); TRY(dalloc(h, &d.relpose, B * (c.n_vo - 1))); TRY(dalloc(h, &d.rollpitch, B * (size_t)c.max_rollpitch));
-    TRY(dalloc(h, &d.n_rp, B));
+    TRY(dalloc(h, &d.imu_sqrt, NI * 225));
     TRY(dalloc(h, &d.strip, F * ISV_PROJ_STRIP)); TRY(dalloc(h, &d.fcost, F));
     TRY(dalloc(h, &d.imu_strip, NI * ISV_IMU_STRIP)); TRY(dalloc(h, &d.imu_cost, NI));
     TRY(dalloc(h, &d.imu_raw, (NI + 7) / 8 * 8 * 144)); HIPCHK(h, hipMemset(d.imu_raw, 0, (NI + 7) / 8 * 8 * 144 * sizeof(double)));      // (ISV_IMU_RAWC = 144, isv_linearize.hip)
     TRY(dalloc(h, &d.prior_strip, B * (size_t)d.prior_strip_sz)); TRY(dalloc(h, &d.prior_cost, B * (size_t)d.n_prior_slots));
-    TRY(dalloc(h, &d.cost, B)); TRY(dalloc(h, &d.st, B));
+    TRY(dalloc(h, &d.cost, B));
     d.prior_H_sz = PH_REL0 + PH_REL_SZ * (c.n_vo - 1) + PH_RP_SZ * c.max_rollpitch;
     TRY(dalloc(h, &d.imu_H, NI * ISV_IMU_H)); TRY(dalloc(h, &d.prior_H, B * (size_t)d.prior_H_sz));
     HIPCHK(h, hipMemset(d.imu_H, 0, NI * ISV_IMU_H * sizeof(double)));      // (the solve kernels read EVERY record and mask the skipped factors' by multiplication: a record that is never written must be finite)
-    TRY(dalloc(h, &d.lm_meta, L));
-    TRY(dalloc(h, &h->Ps0, B * N * 3)); TRY(dalloc(h, &h->Rs0, B * N * 9)); TRY(dalloc(h, &h->Vs0, B * N * 3));
-    TRY(dalloc(h, &h->Bas0, B * N * 3)); TRY(dalloc(h, &h->Bgs0, B * N * 3)); TRY(dalloc(h, &h->depth0, L));
-    TRY(dalloc(h, &h->tic0, B * 3)); TRY(dalloc(h, &h->ric0, B * 9));
-    TRY(dalloc(h, &h->se30, B)); TRY(dalloc(h, &h->lin90, B)); TRY(dalloc(h, &h->relpose0, B * (c.n_vo - 1))); TRY(dalloc(h, &h->rollpitch0, B * (size_t)c.max_rollpitch));
-    auto &s = h->h;
-    TRY(halloc(h, &s.Ps, B * N * 3)); TRY(halloc(h, &s.Rs, B * N * 9)); TRY(halloc(h, &s.Vs, B * N * 3));
-    TRY(halloc(h, &s.Bas, B * N * 3)); TRY(halloc(h, &s.Bgs, B * N * 3)); TRY(halloc(h, &s.tic, B * 3)); TRY(halloc(h, &s.ric, B * 9));
-    TRY(halloc(h, &s.depth, L)); TRY(halloc(h, &s.solve_flag, L)); TRY(halloc(h, &s.lm_pts_i, L * 3)); TRY(halloc(h, &s.f_pts_j, F * 2)); TRY(halloc(h, &s.f_pts_z, F));
-    TRY(halloc(h, &s.imu_in, NI * ISV_IMU_IN)); TRY(halloc(h, &s.imu_cov, NI * 225));
-    TRY(halloc(h, &s.lm_off, B + 1)); TRY(halloc(h, &s.f_off, B + 1)); TRY(halloc(h, &s.lm_host, L)); TRY(halloc(h, &s.lm_k, L)); TRY(halloc(h, &s.lm_f0, L));
-    TRY(halloc(h, &s.tile_win, T)); TRY(halloc(h, &s.tile_f0, T)); TRY(halloc(h, &s.tile_n, T));
-    TRY(halloc(h, &s.pg_perm, F)); TRY(halloc(h, &s.pg_off, B * ((size_t)c.n_frames * (c.n_frames - 1) / 2 + 1)));
-    TRY(halloc(h, &s.pg_sched, B * ((size_t)c.n_frames * (c.n_frames - 1) / 2))); TRY(halloc(h, &s.pg_sched_off, B * (ISV_SWEEP_WAVES + 1))); TRY(halloc(h, &s.imu_skip, NI)); TRY(halloc(h, &s.n_rp, B));
-    TRY(halloc(h, &s.f_rec, F)); TRY(halloc(h, &s.pg_rec, F * 2)); TRY(halloc(h, &s.pg_pts, F * 2)); TRY(halloc(h, &s.pg_wstart, B * (ISV_SWEEP_WAVES + 1)));
-    TRY(halloc(h, &s.margin_old, B)); TRY(halloc(h, &s.header0, B));
-    TRY(halloc(h, &s.lm_meta, L));
-    TRY(halloc(h, &s.lm_optr, L + B)); TRY(halloc(h, &s.obs_raw, F * 3)); TRY(dalloc(h, &h->d_optr, L + B)); TRY(dalloc(h, &h->d_obs_raw, F * 3));
-    h->dev_build = getenv("ISV_HOST_PACK") == nullptr && upload_build_lds_bytes(c.n_frames, c.max_landmarks > 1 ? c.max_landmarks : 1) <= 64 * 1024;
-    TRY(halloc(h, &s.se3, B)); TRY(halloc(h, &s.lin9, B)); TRY(halloc(h, &s.relpose, B * (c.n_vo - 1))); TRY(halloc(h, &s.rollpitch, B * (size_t)c.max_rollpitch));
-    TRY(halloc(h, &s.st, B));
-    TRY(halloc(h, &s.pose, B * N * 7)); TRY(halloc(h, &s.sb, B * N * 9)); TRY(halloc(h, &s.ex, B * 7)); TRY(halloc(h, &s.lam, L));
-    TRY(halloc(h, &h->stage.st, B)); TRY(halloc(h, &h->stage.tc, B * ISV_MAX_TRACE)); TRY(halloc(h, &h->stage.tr, B * ISV_MAX_TRACE));
-    TRY(halloc(h, &h->stage.ts, B * ISV_MAX_TRACE)); TRY(halloc(h, &h->stage.ta, B * ISV_MAX_TRACE)); TRY(halloc(h, &h->stage.marg, B));
     TRY(isv_solver_alloc(h->d, h->hc, B, L, F, h->allocs, h->err));
-    {
-        // (round 5) everything a RAW upload sends lives in ONE pinned block and ONE device block with the same layout, so that an upload
-        // is ONE host-to-device copy: on this GPU a copy command costs 20-50 us of stream time whatever its size (rocprofv3: 30 commands
-        // per upload, 0.7 ms of transfers inside 1.5 ms of stream time).  The arrays were allocated one by one above; they are re-pointed
-        // into the blocks and the originals are released.
-        struct Item { void **hp, **dp; size_t bytes, off; };
-        std::vector<Item> it;
-#define ARENA(hptr, dptr, cnt) it.push_back(Item{(void **)&(hptr), (void **)&(dptr), sizeof(*(hptr)) * (size_t)(cnt), 0})
-        ARENA(s.lm_off, d.lm_off, B + 1); ARENA(s.f_off, d.f_off, B + 1);
-        ARENA(s.Ps, d.Ps, B * N * 3); ARENA(s.Rs, d.Rs, B * N * 9); ARENA(s.Vs, d.Vs, B * N * 3); ARENA(s.Bas, d.Bas, B * N * 3); ARENA(s.Bgs, d.Bgs, B * N * 3);
-        ARENA(s.tic, d.tic, B * 3); ARENA(s.ric, d.ric, B * 9);
-        ARENA(s.se3, d.se3, B); ARENA(s.lin9, d.lin9, B); ARENA(s.relpose, d.relpose, B * (c.n_vo - 1)); ARENA(s.rollpitch, d.rollpitch, B * (size_t)c.max_rollpitch);
-        ARENA(s.depth, d.depth, L);            // (Ps .. depth: what isv_batch_download brings back from this block, in one copy)
-        ARENA(s.n_rp, d.n_rp, B); ARENA(s.margin_old, d.margin_old, B); ARENA(s.header0, d.header0, B);
-        ARENA(s.imu_skip, d.imu_skip, NI); ARENA(s.imu_in, d.imu_in, NI * ISV_IMU_IN); ARENA(s.imu_cov, d.imu_cov, NI * 225);
-        ARENA(s.tile_win, d.tile_win, T); ARENA(s.tile_f0, d.tile_f0, T); ARENA(s.tile_n, d.tile_n, T);
-        ARENA(s.lm_host, d.lm_host, L); ARENA(s.lm_optr, h->d_optr, L + B); ARENA(s.obs_raw, h->d_obs_raw, F * 3);
-#undef ARENA
-        size_t tot = 0;
-        for (Item &q : it) { q.off = tot; tot += (q.bytes + 255) / 256 * 256; }
-        void *hb = nullptr, *db = nullptr;
-        HIPCHK(h, hipHostMalloc(&hb, tot ? tot : 1, hipHostMallocDefault)); h->hallocs.push_back(hb);
-        HIPCHK(h, hipMalloc(&db, tot ? tot : 1)); h->allocs.push_back(db);
-        HIPCHK(h, hipMemset(db, 0, tot ? tot : 1)); memset(hb, 0, tot ? tot : 1);
-        auto drop = [](std::vector<void *> &v, void *p, bool host) { for (size_t i = 0; i < v.size(); i++) if (v[i] == p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); v.erase(v.begin() + i); return; } };
-        for (Item &q : it) {
-            drop(h->hallocs, *q.hp, true); drop(h->allocs, *q.dp, false);
-            *q.hp = (char *)hb + q.off; *q.dp = (char *)db + q.off;
-        }
-        h->arena_h = hb; h->arena_d = db; h->arena_bytes = tot;
-        h->down_a_off = (size_t)((char *)d.Ps - (char *)db); h->down_a_bytes = (size_t)((char *)d.depth - (char *)d.Ps) + sizeof(double) * L;
-        // the solver's outputs: one pinned and one device block as well (a download was 24 copy commands: ~0.8 of its 1.7 ms)
-        std::vector<Item> dn;
-#define ARENA(hptr, dptr, cnt) dn.push_back(Item{(void **)&(hptr), (void **)&(dptr), sizeof(*(hptr)) * (size_t)(cnt), 0})
-        ARENA(s.pose, d.pose, B * N * 7); ARENA(s.sb, d.sb, B * N * 9); ARENA(s.ex, d.ex, B * 7); ARENA(s.lam, d.lam, L); ARENA(s.solve_flag, d.solve_flag, L);
-        ARENA(s.st, d.st, B); ARENA(h->stage.tc, d.trace_cost, B * ISV_MAX_TRACE); ARENA(h->stage.tr, d.trace_radius, B * ISV_MAX_TRACE);
-        ARENA(h->stage.ts, d.trace_step, B * ISV_MAX_TRACE); ARENA(h->stage.ta, d.trace_acc, B * ISV_MAX_TRACE); ARENA(h->stage.marg, d.marg, B);
-#undef ARENA
-        size_t tot2 = 0;
-        for (Item &q : dn) { q.off = tot2; tot2 += (q.bytes + 255) / 256 * 256; }
-        void *hb2 = nullptr, *db2 = nullptr;
-        HIPCHK(h, hipHostMalloc(&hb2, tot2 ? tot2 : 1, hipHostMallocDefault)); h->hallocs.push_back(hb2);
-        HIPCHK(h, hipMalloc(&db2, tot2 ? tot2 : 1)); h->allocs.push_back(db2);
-        HIPCHK(h, hipMemset(db2, 0, tot2 ? tot2 : 1)); memset(hb2, 0, tot2 ? tot2 : 1);
-        for (Item &q : dn) {
-            drop(h->hallocs, *q.hp, true); drop(h->allocs, *q.dp, false);
-            *q.hp = (char *)hb2 + q.off; *q.dp = (char *)db2 + q.off;
-        }
-        drop(h->hallocs, h->stage.st, true); h->stage.st = s.st;      // (the solver's staging of the solve states: the same record)
-        h->down_h = hb2; h->down_d = db2; h->down_bytes = tot2;
-    }
     if (d.est_ex) {
         if (!d.lds_T) { h->err = "estimate_extrinsic = 1 is built for the LDS solver path only (ALL_BUF_SIZE <= 19)"; return ISV_ERR_UNSUPPORTED; }
         const size_t NPr = (size_t)c.n_frames * (c.n_frames - 1) / 2;
@@ -394,160 +349,155 @@ __global__ __launch_bounds__(256) void k_restore(RestoreJobs j) {
 }
 // (save = true: the other direction, at the end of isv_batch_upload -- the twelve hipMemcpyAsync it replaced cost ~0.2 ms of stream time)
 static int restore_initial(isv_backend *h, bool save = false) {
-    DevBatch &d = h->d; const isv_config_t &c = h->cfg; hipStream_t st = h->stream;
-    const size_t n = d.B, N = d.N, L = d.Ltot;
+    const DevBatch &d = h->d;
     RestoreJobs j;
-    int k = 0;
-#define RJOB(dstp, srcp, cnt) do { static_assert(sizeof(*(srcp)) % 8 == 0, "8-byte words"); j.dst[k] = (uint64_t *)(dstp); j.src[k] = (const uint64_t *)(srcp); j.n8[k] = sizeof(*(srcp)) / 8 * (size_t)(cnt); k++; } while (0)
-    RJOB(d.Ps, h->Ps0, n * N * 3); RJOB(d.Rs, h->Rs0, n * N * 9); RJOB(d.Vs, h->Vs0, n * N * 3);
-    RJOB(d.Bas, h->Bas0, n * N * 3); RJOB(d.Bgs, h->Bgs0, n * N * 3); RJOB(d.depth, h->depth0, L);
-    RJOB(d.tic, h->tic0, n * 3); RJOB(d.ric, h->ric0, n * 9);
-    RJOB(d.se3, h->se30, n); RJOB(d.lin9, h->lin90, n); RJOB(d.relpose, h->relpose0, n * (c.n_vo - 1)); RJOB(d.rollpitch, h->rollpitch0, n * c.max_rollpitch);
-#undef RJOB
-    if (save) for (int q = 0; q < k; q++) { uint64_t *t_ = j.dst[q]; j.dst[q] = (uint64_t *)j.src[q]; j.src[q] = t_; }
-    hipLaunchKernelGGL(k_restore, dim3(64, 12), dim3(256), 0, st, j);
+    for_each_batch_buffer(h, BatchDims{(size_t)d.B, (size_t)d.Ltot, 0, 0, 0}, [&](unsigned role, const char *, auto *&, auto *&dp, size_t cnt) {
+        const int k = buf_twin(role);
+        if (k < 0) return;
+        uint64_t *cur = (uint64_t *)dp, *twin = (uint64_t *)h->pristine[k];
+        j.dst[k] = save ? twin : cur; j.src[k] = save ? cur : twin; j.n8[k] = sizeof(*dp) / 8 * cnt;
+    });
+    hipLaunchKernelGGL(k_restore, dim3(64, TW_COUNT), dim3(256), 0, h->stream, j);
     HIPCHK(h, hipGetLastError());
     return ISV_OK;
 }
 
-// pack n caller windows into the pinned staging area and copy them to the device.  Pass 1 (serial) validates the
-// tracks and fixes every window's landmark / factor / tile offsets; pass 2 packs the windows on host threads.
+// ---- isv_batch_upload, step by step ----
+// validate + count: one window's pointers, sizes and landmark tracks, and its landmarks / factors / tiles (-1000: "bad landmark track")
+struct WindowCount { int32_t L, F, T; };
+static int count_window(const isv_config_t &c, const isv_window_t *w, WindowCount &out) {
+    const int N = c.n_frames;
+    if (!w || !w->Ps || !w->Rs || !w->Vs || !w->Bas || !w->Bgs || !w->tic || !w->ric || !w->imu || !w->pose_prior ||
+        !w->vb_prior || !w->relpose || (w->n_rollpitch > 0 && !w->rollpitch) || w->n_landmarks < 0 ||
+        (w->n_landmarks > 0 && (!w->lm_start_frame || !w->lm_obs_ptr || !w->obs_point || !w->lm_depth)))
+        return ISV_ERR_INVALID_ARG;
+    if (w->n_landmarks > c.max_landmarks || w->n_obs > c.max_obs || w->n_rollpitch > c.max_rollpitch) return ISV_ERR_CAPACITY;
+    for (int i = 0; i < w->n_rollpitch; i++) if (w->rollpitch[i].index < 0 || w->rollpitch[i].index >= N) return ISV_ERR_INVALID_ARG;
+    size_t tn = 0, Tw = 0, Fw = 0;
+    for (int l = 0; l < w->n_landmarks; l++) {
+        const int hst = w->lm_start_frame[l], o0 = w->lm_obs_ptr[l], k = w->lm_obs_ptr[l + 1] - o0;
+        if (hst < 0 || k < 2 || hst + k > N || o0 < 0 || o0 + k > w->n_obs) return -1000;
+        if (tn + (size_t)(k - 1) > ISV_TILE) { Tw++; tn = 0; }
+        tn += (size_t)(k - 1);
+        Fw += (size_t)(k - 1);
+    }
+    if (tn) Tw++;
+    out.L = w->n_landmarks; out.F = (int32_t)Fw; out.T = (int32_t)Tw;
+    return ISV_OK;
+}
+
+// the copy plan: how a packed batch goes to the device.  A raw upload (the window as it is: 69 KB per benchmark window against 110 KB of
+// derived arrays, which k_upload_build derives) is ONE copy of the whole upload block while the block is small (a window or two) or the
+// batch uses most of it, and array by array otherwise (a batch far below the handle's capacity).  A large block that K > 1 host threads
+// pack goes up in TWO parts: the first part (states, priors, depths, IMU records: ~45 %) while the threads still pack the second
+// (observations, tiles) -- the copy (1.5 ms for 62 MB) used to start after the whole packing pass.  ISV_UPLOAD_ONE_COPY: test / A-B hook.
+enum CopyPlan { COPY_BLOCK, COPY_TWO_PARTS, COPY_ARRAYS, COPY_HOST_PACKED };
+static CopyPlan choose_copy_plan(const isv_backend *h, const BatchDims &q, int K) {
+    if (!h->dev_build) return COPY_HOST_PACKED;
+    if (h->arena_bytes <= ((size_t)16 << 20)) return COPY_BLOCK;
+    const isv_config_t &c = h->cfg;
+    const size_t Nd = (size_t)h->d.N;        // bytes of the windows in the upload block
+    const size_t used = q.O * 24 + q.L * 16 + q.B * (Nd * 21 * 8 + (Nd - 1) * (289 * 8 + 4) + sizeof(isv_se3_prior_t) + sizeof(isv_linear9_t) +
+                                                      (size_t)(c.n_vo - 1) * sizeof(isv_relpose_t) + (size_t)c.max_rollpitch * sizeof(isv_rollpitch_t));
+    if (used * 10 < h->arena_bytes * 6) return COPY_ARRAYS;
+    return K > 1 && !getenv("ISV_UPLOAD_ONE_COPY") ? COPY_TWO_PARTS : COPY_BLOCK;
+}
+
+// test hook (ISV_DEBUG_UPLOAD_CHECK): pack the same windows on the host as well and compare EVERY derived array with what the device built
+static int check_device_build(isv_backend *h, const BatchDims &q, isv_window_t *const *ws, const std::vector<size_t> &t_off) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int b = 0; b < (int)q.B; b++) { std::string e2; (void)pack_window(h, b, ws[b], (size_t)h->h.lm_off[b], (size_t)h->h.f_off[b], t_off[b], e2, false, true); }
+    int bad = 0;
+    for_each_batch_buffer(h, q, [&](unsigned role, const char *name, auto *&hp, auto *&dp, size_t cnt) {
+        if (!(role & BUF_DERIVED)) return;
+        const size_t bytes = sizeof(*hp) * cnt;
+        std::vector<unsigned char> tmp(bytes ? bytes : 1);
+        if (hipMemcpy(tmp.data(), dp, bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "isv upload check: %s: copy failed\n", name); bad++; return; }
+        if (memcmp(tmp.data(), hp, bytes) != 0) {
+            size_t k = 0; while (k < bytes && tmp[k] == ((const unsigned char *)hp)[k]) k++;
+            fprintf(stderr, "isv upload check: %s differs at byte %zu of %zu\n", name, k, bytes); bad++;
+        }
+    });
+    if (bad) { h->err = "ISV_DEBUG_UPLOAD_CHECK: the device-built arrays differ from the host packer's"; return ISV_ERR_DEVICE; }
+    return ISV_OK;
+}
+
+// pack n caller windows into the pinned staging area, copy them to the device and derive the solver's view of them there.
+// ONE team of host threads (host_threads(n)), spun up once: every thread validates and counts its windows; thread 0 turns the counts
+// into the windows' offsets (a prefix sum over n windows) and chooses the copy plan; every thread packs its windows -- in two phases
+// under the two-part plan, whichever thread finishes the first phase last sending the first part.  The calling thread then sends the
+// rest, enqueues k_upload_build (raw uploads), the pristine copies and k_imu_prep, and waits for the stream.
 extern "C" int isv_batch_upload(isv_backend_t *h, int32_t n, isv_window_t *const *ws) {
     if (!h || !ws || n < 1) return ISV_ERR_INVALID_ARG;
     ENTER(h);
     const auto t_up0 = std::chrono::steady_clock::now();
     if ((size_t)n > h->capB) { h->err = "batch larger than max_batch"; return ISV_ERR_CAPACITY; }
     const isv_config_t &c = h->cfg;
-    const int N = c.n_frames, Nd = h->d.N;
-    auto &s = h->h;
-    size_t L = 0, F = 0, T = 0, Fmax = 0, Lmax = 0;
-    std::vector<size_t> t_off((size_t)n + 1);
+    auto &s = h->h; DevBatch &d = h->d; hipStream_t st = h->stream;
     const bool raw = h->dev_build;
-    DevBatch &d = h->d;
-    hipStream_t st = h->stream;
-    const size_t NIw = (size_t)(Nd - 1);
-    // bytes of the windows in the upload block, and whether the block goes up in two parts (see the packing loop)
-    auto used_bytes = [&]() { return (F + L) * 24 + L * 16 + (size_t)n * ((size_t)Nd * 21 * 8 + NIw * (289 * 8 + 4) + sizeof(isv_se3_prior_t) + sizeof(isv_linear9_t) +
-                                      (size_t)(c.n_vo - 1) * sizeof(isv_relpose_t) + (size_t)c.max_rollpitch * sizeof(isv_rollpitch_t)); };
-    bool split_copy = false;
-    const size_t split_bytes = raw ? (size_t)((char *)d.tile_win - (char *)h->arena_d) : 0;
-    std::atomic<int> phase_a_done{0}, copy_failed{0}, first_sent{0};
-    // ONE team of host threads, three phases (round 5; the counting pass used to run on the calling thread alone: 0.7 of the 2.0 ms):
-    //   1. every thread validates its windows' tracks and counts their landmarks / factors / tiles;
-    //   2. thread 0 turns the counts into the windows' offsets (a prefix sum over n windows);
-    //   3. every thread packs its windows into the pinned staging area.
-    struct Cnt { int32_t L, F, T; int rc; };
-    std::vector<Cnt> cnt((size_t)n);
-    auto count_window = [&](int b) -> int {
-        const isv_window_t *w = ws[b];
-        if (!w || !w->Ps || !w->Rs || !w->Vs || !w->Bas || !w->Bgs || !w->tic || !w->ric || !w->imu || !w->pose_prior ||
-            !w->vb_prior || !w->relpose || (w->n_rollpitch > 0 && !w->rollpitch) || w->n_landmarks < 0 ||
-            (w->n_landmarks > 0 && (!w->lm_start_frame || !w->lm_obs_ptr || !w->obs_point || !w->lm_depth)))
-            return ISV_ERR_INVALID_ARG;
-        if (w->n_landmarks > c.max_landmarks || w->n_obs > c.max_obs || w->n_rollpitch > c.max_rollpitch) return ISV_ERR_CAPACITY;
-        for (int i = 0; i < w->n_rollpitch; i++) if (w->rollpitch[i].index < 0 || w->rollpitch[i].index >= N) return ISV_ERR_INVALID_ARG;
-        size_t tn = 0, Tw = 0, Fw = 0;
-        for (int l = 0; l < w->n_landmarks; l++) {
-            const int hst = w->lm_start_frame[l], o0 = w->lm_obs_ptr[l], k = w->lm_obs_ptr[l + 1] - o0;
-            if (hst < 0 || k < 2 || hst + k > N || o0 < 0 || o0 + k > w->n_obs) return -1000;      // "bad landmark track"
-            if (tn + (size_t)(k - 1) > ISV_TILE) { Tw++; tn = 0; }
-            tn += (size_t)(k - 1);
-            Fw += (size_t)(k - 1);
+    const int K = host_threads(n);
+    std::vector<WindowCount> cnt((size_t)n);
+    std::vector<size_t> t_off((size_t)n + 1);
+    std::vector<int> rcs((size_t)K, ISV_OK);
+    std::vector<std::string> errs((size_t)K);
+    BatchDims q{};
+    size_t Fmax = 0, Lmax = 0;
+    CopyPlan plan = COPY_BLOCK;
+    std::atomic<int> counted{0}, offsets_ready{0}, phase_a_done{0}, copy_failed{0};
+    auto all_ok = [&]() { bool ok = true; for (int k = 0; k < K; k++) ok &= rcs[k] == ISV_OK; return ok; };
+    // offsets + copy plan (thread 0, once every thread has counted)
+    auto offsets_and_plan = [&]() {
+        size_t L = 0, F = 0, T = 0;
+        for (int b = 0; b < n; b++) {
+            s.lm_off[b] = (int32_t)L; s.f_off[b] = (int32_t)F; t_off[b] = T;
+            L += (size_t)cnt[b].L; F += (size_t)cnt[b].F; T += (size_t)cnt[b].T;
+            if ((size_t)cnt[b].F > Fmax) Fmax = (size_t)cnt[b].F;
+            if ((size_t)cnt[b].L > Lmax) Lmax = (size_t)cnt[b].L;
         }
-        if (tn) Tw++;
-        cnt[b].L = w->n_landmarks; cnt[b].F = (int32_t)Fw; cnt[b].T = (int32_t)Tw;
-        return ISV_OK;
+        t_off[n] = T; s.lm_off[n] = (int32_t)L; s.f_off[n] = (int32_t)F;
+        q = BatchDims{(size_t)n, L, F, F + L, T};
+        h->resident = 0;           // (from here on the staging area and, with the two-part copy, the device block are being overwritten)
+        plan = choose_copy_plan(h, q, K);
+    };
+    // pack (phase 0: whole windows; 1 / 2: the first / second part of the upload block)
+    auto pack = [&](int k, int b0, int b1, int phase) {
+        for (int b = b0; b < b1; b++) {
+            const int rc = pack_window(h, b, ws[b], (size_t)s.lm_off[b], (size_t)s.f_off[b], t_off[b], errs[k], raw, true, phase);
+            if (rc != ISV_OK) { rcs[k] = rc; return; }
+        }
+    };
+    auto work = [&](int k) {
+        const int b0 = (int)((int64_t)n * k / K), b1 = (int)((int64_t)n * (k + 1) / K);
+        for (int b = b0; b < b1 && rcs[k] == ISV_OK; b++) rcs[k] = count_window(c, ws[b], cnt[b]);
+        counted.fetch_add(1, std::memory_order_release);
+        if (k == 0) {
+            while (counted.load(std::memory_order_acquire) < K) std::this_thread::yield();
+            const bool ok = all_ok();
+            if (ok) offsets_and_plan();
+            offsets_ready.store(ok ? 1 : -1, std::memory_order_release);
+        }
+        int ready;
+        while ((ready = offsets_ready.load(std::memory_order_acquire)) == 0) std::this_thread::yield();
+        if (ready < 0) return;
+        if (plan != COPY_TWO_PARTS) { pack(k, b0, b1, 0); return; }
+        pack(k, b0, b1, 1);
+        if (phase_a_done.fetch_add(1, std::memory_order_acq_rel) == K - 1 && all_ok() &&
+            (hipSetDevice(h->device) != hipSuccess || hipMemcpyAsync(h->arena_d, h->arena_h, h->split_bytes, hipMemcpyHostToDevice, st) != hipSuccess)) copy_failed.store(1);
+        if (rcs[k] == ISV_OK) pack(k, b0, b1, 2);
     };
     {
-        const int K = host_threads(n);
-        std::vector<int> rcs((size_t)K, ISV_OK);
-        std::vector<std::string> errs((size_t)K);
-        std::atomic<int> counted{0}, offsets_ready{0};
-        auto work = [&](int k) {
-            const int b0 = (int)((int64_t)n * k / K), b1 = (int)((int64_t)n * (k + 1) / K);
-            for (int b = b0; b < b1 && rcs[k] == ISV_OK; b++) rcs[k] = count_window(b);
-            counted.fetch_add(1, std::memory_order_release);
-            if (k == 0) {
-                while (counted.load(std::memory_order_acquire) < K) std::this_thread::yield();
-                bool ok = true;
-                for (int q = 0; q < K; q++) ok &= rcs[q] == ISV_OK;
-                if (ok) {
-                    for (int b = 0; b < n; b++) {
-                        s.lm_off[b] = (int32_t)L; s.f_off[b] = (int32_t)F; t_off[b] = T;
-                        L += (size_t)cnt[b].L; F += (size_t)cnt[b].F; T += (size_t)cnt[b].T;
-                        if ((size_t)cnt[b].F > Fmax) Fmax = (size_t)cnt[b].F;
-                        if ((size_t)cnt[b].L > Lmax) Lmax = (size_t)cnt[b].L;
-                    }
-                    t_off[n] = T; s.lm_off[n] = (int32_t)L; s.f_off[n] = (int32_t)F;
-                    h->resident = 0;           // (from here on the staging area and, with the two-part copy, the device block are being overwritten)
-                    split_copy = raw && K > 1 && h->arena_bytes > ((size_t)16 << 20) && used_bytes() * 10 >= h->arena_bytes * 6 && !getenv("ISV_UPLOAD_ONE_COPY");
-                }
-                offsets_ready.store(ok ? 1 : -1, std::memory_order_release);
-            }
-            int ready;
-            while ((ready = offsets_ready.load(std::memory_order_acquire)) == 0) std::this_thread::yield();
-            if (ready < 0) return;
-            // (round 5) a raw upload that goes up as one block is packed in TWO phases -- the first part of the block (states, priors, depths,
-            // IMU records: ~45 %) and the rest (observations, tiles) -- and whichever thread finishes the first phase last sends the first
-            // part while every thread packs the second: the copy (1.5 ms for 62 MB) used to start after the whole packing pass
-            if (split_copy) {
-                for (int b = b0; b < b1; b++) {
-                    const int rc = pack_window(h, b, ws[b], (size_t)s.lm_off[b], (size_t)s.f_off[b], t_off[b], errs[k], raw, true, 1);
-                    if (rc != ISV_OK) { rcs[k] = rc; break; }
-                }
-                if (phase_a_done.fetch_add(1, std::memory_order_acq_rel) == K - 1) {
-                    bool okA = true;
-                    for (int q = 0; q < K; q++) okA &= rcs[q] == ISV_OK;
-                    if (okA && (hipSetDevice(h->device) != hipSuccess || hipMemcpyAsync(h->arena_d, h->arena_h, split_bytes, hipMemcpyHostToDevice, st) != hipSuccess)) copy_failed.store(1);
-                    if (okA) first_sent.store(1, std::memory_order_release);
-                }
-                if (rcs[k] != ISV_OK) return;
-                for (int b = b0; b < b1; b++) {
-                    const int rc = pack_window(h, b, ws[b], (size_t)s.lm_off[b], (size_t)s.f_off[b], t_off[b], errs[k], raw, true, 2);
-                    if (rc != ISV_OK) { rcs[k] = rc; return; }
-                }
-                return;
-            }
-            for (int b = b0; b < b1; b++) {
-                const int rc = pack_window(h, b, ws[b], (size_t)s.lm_off[b], (size_t)s.f_off[b], t_off[b], errs[k], raw, true);
-                if (rc != ISV_OK) { rcs[k] = rc; return; }
-            }
-        };
-        if (K == 1) work(0);
-        else {
-            std::vector<std::thread> th;
-            for (int k = 1; k < K; k++) th.emplace_back(work, k);
-            work(0);
-            for (auto &t : th) t.join();
-        }
-        for (int k = 0; k < K; k++) if (rcs[k] != ISV_OK) {
-            if (rcs[k] == -1000) { h->err = "bad landmark track"; return ISV_ERR_INVALID_ARG; }
-            if (rcs[k] == ISV_ERR_CAPACITY && errs[k].empty()) h->err = "window exceeds capacity"; else if (!errs[k].empty()) h->err = errs[k];
-            return rcs[k];
-        }
+        std::vector<std::thread> th;
+        for (int k = 1; k < K; k++) th.emplace_back(work, k);
+        work(0);
+        for (auto &t : th) t.join();
     }
-    // the copies of a raw upload when the one-block copy below does not pay (a batch far below the handle's capacity): array by array
-    auto enqueue_arrays = [&](int b0, int b1) -> int {
-#define H2DC(dst, src, off, cnt) do { if ((cnt) > 0 && hipMemcpyAsync((dst) + (off), (src) + (off), sizeof(*(src)) * (size_t)(cnt), hipMemcpyHostToDevice, st) != hipSuccess) return ISV_ERR_DEVICE; } while (0)
-        const size_t nb = (size_t)(b1 - b0), l0 = (size_t)s.lm_off[b0], l1 = (size_t)s.lm_off[b1], f0 = (size_t)s.f_off[b0], f1 = (size_t)s.f_off[b1];
-        H2DC(d.Ps, s.Ps, (size_t)b0 * Nd * 3, nb * Nd * 3); H2DC(d.Rs, s.Rs, (size_t)b0 * Nd * 9, nb * Nd * 9); H2DC(d.Vs, s.Vs, (size_t)b0 * Nd * 3, nb * Nd * 3);
-        H2DC(d.Bas, s.Bas, (size_t)b0 * Nd * 3, nb * Nd * 3); H2DC(d.Bgs, s.Bgs, (size_t)b0 * Nd * 3, nb * Nd * 3);
-        H2DC(d.tic, s.tic, (size_t)b0 * 3, nb * 3); H2DC(d.ric, s.ric, (size_t)b0 * 9, nb * 9);
-        H2DC(d.depth, s.depth, l0, l1 - l0); H2DC(d.lm_host, s.lm_host, l0, l1 - l0);
-        H2DC(h->d_optr, s.lm_optr, l0 + b0, (l1 - l0) + nb); H2DC(h->d_obs_raw, s.obs_raw, (f0 + l0) * 3, ((f1 + l1) - (f0 + l0)) * 3);
-        H2DC(d.imu_in, s.imu_in, (size_t)b0 * NIw * ISV_IMU_IN, nb * NIw * ISV_IMU_IN); H2DC(d.imu_cov, s.imu_cov, (size_t)b0 * NIw * 225, nb * NIw * 225);
-        H2DC(d.imu_skip, s.imu_skip, (size_t)b0 * NIw, nb * NIw);
-        H2DC(d.se3, s.se3, (size_t)b0, nb); H2DC(d.lin9, s.lin9, (size_t)b0, nb); H2DC(d.relpose, s.relpose, (size_t)b0 * (c.n_vo - 1), nb * (c.n_vo - 1));
-        H2DC(d.rollpitch, s.rollpitch, (size_t)b0 * c.max_rollpitch, nb * c.max_rollpitch);
-        H2DC(d.n_rp, s.n_rp, (size_t)b0, nb); H2DC(d.margin_old, s.margin_old, (size_t)b0, nb); H2DC(d.header0, s.header0, (size_t)b0, nb);
-        // (the tiles of k_proj_linearize: the linearise API reads them whatever the solver runs; built on the host, a counting loop)
-        H2DC(d.tile_win, s.tile_win, t_off[b0], t_off[b1] - t_off[b0]); H2DC(d.tile_f0, s.tile_f0, t_off[b0], t_off[b1] - t_off[b0]); H2DC(d.tile_n, s.tile_n, t_off[b0], t_off[b1] - t_off[b0]);
-        H2DC(d.lm_off, s.lm_off, 0, (size_t)n + 1); H2DC(d.f_off, s.f_off, 0, (size_t)n + 1);
-#undef H2DC
-        return ISV_OK;
-    };
+    for (int k = 0; k < K; k++) if (rcs[k] != ISV_OK) {
+        if (rcs[k] == -1000) { h->err = "bad landmark track"; return ISV_ERR_INVALID_ARG; }
+        if (rcs[k] == ISV_ERR_CAPACITY && errs[k].empty()) h->err = "window exceeds capacity"; else if (!errs[k].empty()) h->err = errs[k];
+        return rcs[k];
+    }
     const auto t_packed = std::chrono::steady_clock::now();
-    d.B = n; d.Ltot = (int32_t)L; d.Ftot = (int32_t)F; d.n_tiles = (int32_t)T;
+    d.B = n; d.Ltot = (int32_t)q.L; d.Ftot = (int32_t)q.F; d.n_tiles = (int32_t)q.T;
     d.seq_hdr = nullptr;                       // (the upload path: every window of the batch is solved)
     // k_lin_gram takes one window per workgroup: right for windows of ordinary length, whatever the handle's capacity is
     // (the reference-shaped handle reserves NUM_OF_F x ALL_BUF_SIZE = 18 000 observations and sees ~2 000 factors).  A
@@ -561,58 +511,21 @@ extern "C" int isv_batch_upload(isv_backend_t *h, int32_t n, isv_window_t *const
     const bool lg_fits = lin_gram_lds_bytes(c.n_frames, true, c.estimate_extrinsic != 0, LG_WAVES, d.lg_lcap) <= ISV_LDS_PER_CU;
     if (c.estimate_extrinsic && !lg_fits) { h->err = "estimate_extrinsic = 1: a window has more landmarks than k_lin_gram<true> can stage in LDS"; return ISV_ERR_CAPACITY; }
     d.fused_visual = (c.estimate_extrinsic || !(h->hc.legacy_visual || Fmax > ISV_FUSED_MAX_FACTORS || !lg_fits)) ? 1 : 0;
-#define H2D(dst, src, cnt) HIPCHK(h, hipMemcpyAsync(dst, src, sizeof(*(src)) * (size_t)(cnt), hipMemcpyHostToDevice, st))
-    const size_t NI = (size_t)n * (Nd - 1);
-    if (raw) {
-        // the raw CSR goes up (69 KB per benchmark window against 110 KB of derived arrays) and the device derives the rest.  ONE copy of
-        // the whole block while the batch uses most of it (or the block is small: a window or two); array by array otherwise.
-        const size_t used = used_bytes();
-        if (copy_failed.load()) { h->err = "isv_batch_upload: host-to-device copy failed"; return ISV_ERR_DEVICE; }
-        if (first_sent.load(std::memory_order_acquire)) HIPCHK(h, hipMemcpyAsync((char *)h->arena_d + split_bytes, (char *)h->arena_h + split_bytes, h->arena_bytes - split_bytes, hipMemcpyHostToDevice, st));     // (the first part went up during the packing pass)
-        else if (h->arena_bytes <= ((size_t)16 << 20) || used * 10 >= h->arena_bytes * 6) HIPCHK(h, hipMemcpyAsync(h->arena_d, h->arena_h, h->arena_bytes, hipMemcpyHostToDevice, st));
-        else if (enqueue_arrays(0, n) != ISV_OK) { h->err = "isv_batch_upload: host-to-device copy failed"; return ISV_ERR_DEVICE; }
-        if (isv_upload_build_enqueue(d, h->d_optr, h->d_obs_raw, c.max_landmarks > 1 ? c.max_landmarks : 1, st) != ISV_OK) { h->err = "k_upload_build launch failed"; return ISV_ERR_DEVICE; }
-        if (getenv("ISV_DEBUG_UPLOAD_CHECK")) {
-            // test hook: pack the same windows on the host as well and compare EVERY derived array with what the device built
-            HIPCHK(h, hipStreamSynchronize(st));
-            for (int b = 0; b < n; b++) { std::string e2; (void)pack_window(h, b, ws[b], (size_t)s.lm_off[b], (size_t)s.f_off[b], t_off[b], e2, false, true); }
-            const size_t NPp = (size_t)N * (N - 1) / 2;
-            int bad = 0;
-            auto cmp = [&](const char *name, const void *host, const void *dev, size_t bytes) {
-                std::vector<unsigned char> tmp(bytes ? bytes : 1);
-                if (hipMemcpy(tmp.data(), dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "isv upload check: %s: copy failed\n", name); bad++; return; }
-                if (memcmp(tmp.data(), host, bytes) != 0) {
-                    size_t k = 0; while (k < bytes && tmp[k] == ((const unsigned char *)host)[k]) k++;
-                    fprintf(stderr, "isv upload check: %s differs at byte %zu of %zu\n", name, k, bytes); bad++;
-                }
-            };
-            cmp("lm_k", s.lm_k, d.lm_k, L * 4); cmp("lm_f0", s.lm_f0, d.lm_f0, L * 4); cmp("lm_meta", s.lm_meta, d.lm_meta, L * 4); cmp("lm_pts_i", s.lm_pts_i, d.lm_pts_i, L * 24);
-            cmp("f_rec", s.f_rec, d.f_rec, F * sizeof(FactorRec)); cmp("f_pts_j", s.f_pts_j, d.f_pts_j, F * 16); cmp("f_pts_z", s.f_pts_z, d.f_pts_z, F * 8);
-            cmp("pg_perm", s.pg_perm, d.pg_perm, F * 4); cmp("pg_off", s.pg_off, d.pg_off, (size_t)n * (NPp + 1) * 4); cmp("pg_sched", s.pg_sched, d.pg_sched, (size_t)n * NPp * 4);
-            cmp("pg_sched_off", s.pg_sched_off, d.pg_sched_off, (size_t)n * (ISV_SWEEP_WAVES + 1) * 4); cmp("pg_wstart", s.pg_wstart, d.pg_wstart, (size_t)n * (ISV_SWEEP_WAVES + 1) * 4);
-            cmp("pg_rec", s.pg_rec, d.pg_rec, F * 8); cmp("pg_pts", s.pg_pts, d.pg_pts, F * 16);
-            if (bad) { h->err = "ISV_DEBUG_UPLOAD_CHECK: the device-built arrays differ from the host packer's"; return ISV_ERR_DEVICE; }
-        }
-    } else {
-    H2D(d.lm_off, s.lm_off, n + 1); H2D(d.f_off, s.f_off, n + 1);
-    H2D(d.Ps, s.Ps, (size_t)n * Nd * 3); H2D(d.Rs, s.Rs, (size_t)n * Nd * 9); H2D(d.Vs, s.Vs, (size_t)n * Nd * 3);
-    H2D(d.Bas, s.Bas, (size_t)n * Nd * 3); H2D(d.Bgs, s.Bgs, (size_t)n * Nd * 3); H2D(d.tic, s.tic, (size_t)n * 3); H2D(d.ric, s.ric, (size_t)n * 9);
-    H2D(d.depth, s.depth, L);
-    H2D(d.lm_host, s.lm_host, L);
-    H2D(d.lm_k, s.lm_k, L); H2D(d.lm_f0, s.lm_f0, L); H2D(d.lm_pts_i, s.lm_pts_i, L * 3);
-    H2D(d.f_rec, s.f_rec, F); H2D(d.f_pts_j, s.f_pts_j, F * 2); H2D(d.f_pts_z, s.f_pts_z, F);
-    H2D(d.lm_meta, s.lm_meta, L);
-    H2D(d.tile_win, s.tile_win, T); H2D(d.tile_f0, s.tile_f0, T); H2D(d.tile_n, s.tile_n, T);
-    H2D(d.pg_rec, s.pg_rec, F * 2); H2D(d.pg_pts, s.pg_pts, F * 2); H2D(d.pg_wstart, s.pg_wstart, (size_t)n * (ISV_SWEEP_WAVES + 1));
-    H2D(d.pg_perm, s.pg_perm, F); H2D(d.pg_off, s.pg_off, (size_t)n * ((size_t)N * (N - 1) / 2 + 1));
-    H2D(d.pg_sched, s.pg_sched, (size_t)n * ((size_t)N * (N - 1) / 2)); H2D(d.pg_sched_off, s.pg_sched_off, (size_t)n * (ISV_SWEEP_WAVES + 1));
-    H2D(d.imu_in, s.imu_in, NI * ISV_IMU_IN); H2D(d.imu_cov, s.imu_cov, NI * 225); H2D(d.imu_skip, s.imu_skip, NI);
-    H2D(d.se3, s.se3, n); H2D(d.lin9, s.lin9, n); H2D(d.relpose, s.relpose, (size_t)n * (c.n_vo - 1)); H2D(d.rollpitch, s.rollpitch, (size_t)n * c.max_rollpitch);
-    H2D(d.n_rp, s.n_rp, n); H2D(d.margin_old, s.margin_old, n); H2D(d.header0, s.header0, n);
+    // send the rest
+    if (copy_failed.load()) { h->err = "isv_batch_upload: host-to-device copy failed"; return ISV_ERR_DEVICE; }
+    switch (plan) {
+    case COPY_TWO_PARTS: HIPCHK(h, hipMemcpyAsync((char *)h->arena_d + h->split_bytes, (char *)h->arena_h + h->split_bytes, h->arena_bytes - h->split_bytes, hipMemcpyHostToDevice, st)); break;
+    case COPY_BLOCK: HIPCHK(h, hipMemcpyAsync(h->arena_d, h->arena_h, h->arena_bytes, hipMemcpyHostToDevice, st)); break;
+    case COPY_ARRAYS: HIPCHK(h, copy_batch_buffers(h, q, BUF_UPLOAD, 0, true)); break;
+    case COPY_HOST_PACKED: HIPCHK(h, copy_batch_buffers(h, q, BUF_UPLOAD | BUF_DERIVED, BUF_RAW, true)); break;
     }
-#undef H2D
+    if (raw) {
+        if (isv_upload_build_enqueue(d, h->d_optr, h->d_obs_raw, c.max_landmarks > 1 ? c.max_landmarks : 1, st) != ISV_OK) { h->err = "k_upload_build launch failed"; return ISV_ERR_DEVICE; }
+        if (getenv("ISV_DEBUG_UPLOAD_CHECK")) TRY(check_device_build(h, q, ws, t_off));
+    }
     TRY(restore_initial(h, true));              // the pristine copies isv_batch_optimize starts from
     // IMU sqrt_info once per upload (the covariances do not change during a solve)
+    const size_t NI = (size_t)n * (d.N - 1);
     if (NI) hipLaunchKernelGGL(k_imu_prep, dim3((unsigned)NI), dim3(64), 0, st, d, (const int32_t *)nullptr);
     HIPCHK(h, hipGetLastError());
     const auto t_enq = std::chrono::steady_clock::now();
@@ -761,28 +674,23 @@ extern "C" int isv_batch_optimize(isv_backend_t *h, int32_t sync) {
     return ISV_OK;
 }
 
+// bring the solved batch back into the pinned staging area and unpack it into the n caller windows (and their summaries /
+// marginalisation records) on host threads.
 extern "C" int isv_batch_download(isv_backend_t *h, int32_t n, isv_window_t *const *ws, isv_summary_t *summary,
                                   isv_marg_result_t *marg) {
     if (!h || !ws || n != h->resident) return ISV_ERR_INVALID_ARG;
     ENTER(h);
     DevBatch &d = h->d; hipStream_t st = h->stream; auto &s = h->h; const isv_config_t &c = h->cfg;
-    const size_t N = d.N, Nr = d.Nr, L = d.Ltot;          // device stride (incl. the extrinsic's pseudo-frame), real frames
-#define D2H(dst, src, cnt) HIPCHK(h, hipMemcpyAsync(dst, src, sizeof(*(src)) * (size_t)(cnt), hipMemcpyDeviceToHost, st))
+    const size_t N = d.N, Nr = d.Nr;          // device stride (incl. the extrinsic's pseudo-frame), real frames
     // (round 5) a batch that uses most of the handle comes back in TWO copies (a copy command costs 20-50 us of stream time whatever its
     // size: the 24 of the array-by-array form were ~0.8 ms of a 1024-window download's 1.7); a small one array by array
     const bool two_copies = h->down_bytes > 0 && (size_t)n * 2 >= (size_t)c.max_batch && !getenv("ISV_DOWNLOAD_ARRAYS");
     if (two_copies) {
         HIPCHK(h, hipMemcpyAsync((char *)h->arena_h + h->down_a_off, (char *)h->arena_d + h->down_a_off, h->down_a_bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(h->down_h, h->down_d, h->down_bytes, hipMemcpyDeviceToHost, st));
-    } else {
-    D2H(s.Ps, d.Ps, n * N * 3); D2H(s.Rs, d.Rs, n * N * 9); D2H(s.Vs, d.Vs, n * N * 3); D2H(s.Bas, d.Bas, n * N * 3); D2H(s.Bgs, d.Bgs, n * N * 3);
-    D2H(s.tic, d.tic, (size_t)n * 3); D2H(s.ric, d.ric, (size_t)n * 9); D2H(s.depth, d.depth, L); D2H(s.solve_flag, d.solve_flag, L);
-    D2H(s.se3, d.se3, n); D2H(s.lin9, d.lin9, n); D2H(s.relpose, d.relpose, (size_t)n * (c.n_vo - 1)); D2H(s.rollpitch, d.rollpitch, (size_t)n * c.max_rollpitch);
-    D2H(s.pose, d.pose, n * N * 7); D2H(s.sb, d.sb, n * N * 9); D2H(s.ex, d.ex, (size_t)n * 7); D2H(s.lam, d.lam, L);
-    D2H(s.st, d.st, n);
-    }
+    } else HIPCHK(h, copy_batch_buffers(h, BatchDims{(size_t)n, (size_t)d.Ltot, 0, 0, 0}, BUF_BACK | BUF_STATE, 0, false));
     HIPCHK(h, hipStreamSynchronize(st));
-    if (!two_copies) { int rcs = isv_solver_download(h->d, st, n, h->stage, summary, marg, h->err); if (rcs != ISV_OK) return rcs; }      // (two copies: the records are here already; unpacked per window below)
+    if (!two_copies) TRY(isv_solver_download(h, n, summary, marg));      // (two copies: the records are here already; unpacked per window below)
     auto unpack = [&](int b) {
         isv_window_t *w = ws[b];
         memcpy(w->Ps, s.Ps + (size_t)b * N * 3, sizeof(double) * Nr * 3); memcpy(w->Rs, s.Rs + (size_t)b * N * 9, sizeof(double) * Nr * 9);
@@ -884,6 +792,7 @@ extern "C" int isv_backend_init_factor_graph(isv_backend_t *h, isv_window_t *w, 
 
 // FeatureManager::triangulate (src/feature_tracker/feature_manager.cpp:206-258) for every landmark of the n windows whose
 // estimated depth is not positive: DLT over all its views, smallest right singular vector, clamp to INIT_DEPTH.
+#define D2H(dst, src, cnt) HIPCHK(h, hipMemcpyAsync(dst, src, sizeof(*(src)) * (size_t)(cnt), hipMemcpyDeviceToHost, st))
 extern "C" int isv_backend_triangulate(isv_backend_t *h, int32_t n, isv_window_t *const *ws) {
     TRY(isv_batch_upload(h, n, ws));
     DevBatch &d = h->d; hipStream_t st = h->stream; auto &s = h->h;
@@ -912,7 +821,7 @@ extern "C" int isv_backend_solve_odometry_batch(isv_backend_t *h, int32_t n, isv
     if (d.Ltot) {
         hipLaunchKernelGGL(k_triangulate, dim3((d.Ltot + 63) / 64), dim3(64), 0, st, d);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h->depth0, d.depth, sizeof(double) * (size_t)d.Ltot, hipMemcpyDeviceToDevice, st));        // isv_batch_optimize restores the state from the *0 copies
+        HIPCHK(h, hipMemcpyAsync(h->pristine[TW_depth], d.depth, sizeof(double) * (size_t)d.Ltot, hipMemcpyDeviceToDevice, st));        // isv_batch_optimize restores the state from the pristine copies
     }
     TRY(isv_batch_optimize(h, 1));
     const auto t2 = std::chrono::steady_clock::now();

@@ -26,6 +26,12 @@ struct InitSlot {
     double call_ms = 0, kernel_ms = 0;
 };
 
+// a block of buffers, laid out section by section: each starts 256-byte aligned (the kernels read every section by pointer)
+struct BlockLayout {
+    size_t end = 0;
+    size_t add(size_t bytes) { const size_t o = end; end += (bytes + 255) & ~(size_t)255; return o; }
+};
+
 struct isv_backend {
     isv_config_t cfg;
     std::string err;
@@ -54,10 +60,10 @@ struct isv_backend {
     } h{};
     SolverStage stage{};          // pinned staging of the result records
     std::vector<void *> hallocs;
-    // pristine copies for isv_batch_optimize restore
-    double *Ps0 = nullptr, *Rs0 = nullptr, *Vs0 = nullptr, *Bas0 = nullptr, *Bgs0 = nullptr, *depth0 = nullptr, *tic0 = nullptr, *ric0 = nullptr;
-    isv_se3_prior_t *se30 = nullptr; isv_linear9_t *lin90 = nullptr; isv_relpose_t *relpose0 = nullptr; isv_rollpitch_t *rollpitch0 = nullptr;
-    void *arena_h = nullptr, *arena_d = nullptr; size_t arena_bytes = 0;      // the raw upload's arrays, one pinned and one device block of the same layout (one copy per upload)
+    void *pristine[12] = {};      // device copies of what was uploaded, one per buffer with a twin (TW_* in isv_batch_buffers.h): isv_batch_optimize starts from them
+    // the raw upload's arrays, one pinned and one device block of the same layout (isv_batch_buffers.h): one copy per upload, or two
+    // -- [0, split_bytes) while the host threads still pack the rest
+    void *arena_h = nullptr, *arena_d = nullptr; size_t arena_bytes = 0, split_bytes = 0;
     // (round 5) isv_batch_download in TWO copies: the window's state / priors / depths sit next to each other inside the upload block
     // (down_a_off .. + down_a_bytes), the solver's outputs (tangent state, depth flags, traces, marginalisation records) in a block of their own
     size_t down_a_off = 0, down_a_bytes = 0;

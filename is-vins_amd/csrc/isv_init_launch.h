@@ -9,12 +9,6 @@
 #include <vector>
 #include "isv_backend_impl.h"
 
-// a stage's device block, laid out section by section: each starts 256-byte aligned (the kernels read every section by pointer)
-struct InitLayout {
-    size_t end = 0;
-    size_t add(size_t bytes) { const size_t o = end; end += (bytes + 255) & ~(size_t)255; return o; }
-};
-
 struct InitCopy { void *dst; size_t off, bytes; };   // a device-to-host copy out of the block (skipped when dst is null)
 
 struct InitCall {

@@ -524,7 +524,7 @@ extern "C" int isv_internal_visual_imu_align_batch(isv_backend_t *h, int32_t n, 
     }
     if (n_frames > INT32_MAX || n_imu > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
     // one upload block: [headers | frames | imu rows]; then, device only: results
-    InitLayout L;
+    BlockLayout L;
     const size_t o_hd = L.add(sizeof(ProbHdr) * n), o_fr = L.add(sizeof(isv_align_frame_t) * n_frames), o_imu = L.add(sizeof(double) * 7 * (n_imu ? n_imu : 1));
     std::vector<char> up(L.end);
     const size_t o_res = L.add(sizeof(isv_align_result_t) * n);

@@ -93,6 +93,6 @@ hipError_t isv_raise_dynamic_lds(const void *fn, int device, size_t lds);
 // isv_batch_upload's device half (isv_sequence.hip): raw CSR -> lm_* / f_* / pg_* arrays
 size_t upload_build_lds_bytes(int N, int lcap);
 int isv_upload_build_enqueue(DevBatch &d, const int32_t *optr, const double *obs_raw, int lcap, hipStream_t st);
-int isv_solver_download(DevBatch &d, hipStream_t st, int n, const SolverStage &stage, isv_summary_t *summary, isv_marg_result_t *marg, std::string &err, bool staged = false);
+int isv_solver_download(struct isv_backend *h, int n, isv_summary_t *summary, isv_marg_result_t *marg);
 void isv_solver_unpack_window(const SolverStage &stage, int b, isv_summary_t *summary, isv_marg_result_t *marg);
 int isv_solver_debug_read(DevBatch &d, hipStream_t st, int what, double *out, int64_t count, std::string &err);

@@ -246,7 +246,7 @@ extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv
     }
     if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_fr > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
     // one upload block: [headers | tracks | obs | dv | sdt]; then, device only: results (zeroed before the launch), per-track masks
-    InitLayout L;
+    BlockLayout L;
     const size_t o_hd = L.add(sizeof(RpHdr) * n), o_tr = L.add(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_obs = L.add(16 * (n_obs + 1));
     const size_t o_dv = L.add(24 * (n_fr + 1)), o_sdt = L.add(8 * (n_fr + 1));
     std::vector<char> up(L.end);

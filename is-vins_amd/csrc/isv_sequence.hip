@@ -21,7 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "isv_backend_impl.h"
+#include "isv_batch_buffers.h"
 
 #define ISV_SEQ_RING 32                 // observation ring of a track (>= ISV_MAX_FRAMES, power of two)
 #define SEQ_HDR 8                       // ints of the per-window frame header
@@ -649,8 +649,9 @@ extern "C" int isv_backend_seq_enable(isv_backend_t *h, int32_t tracks_per_windo
     TRY(halloc(h, &q->h_imu_in, B * 2 * ISV_IMU_IN)); TRY(halloc(h, &q->h_imu_cov, B * 2 * 225)); TRY(halloc(h, &q->h_imu_skip, B * 2));
     TRY(halloc(h, &q->h_out, B * SEQ_OUT)); TRY(halloc(h, &q->h_flags, h->capL));
     HIPCHK(h, hipMemset(s.err, 0, B * sizeof(int32_t)));
-    s.Ps0 = h->Ps0; s.Rs0 = h->Rs0; s.Vs0 = h->Vs0; s.Bas0 = h->Bas0; s.Bgs0 = h->Bgs0;
-    s.se30 = h->se30; s.lin90 = h->lin90; s.relpose0 = h->relpose0; s.rollpitch0 = h->rollpitch0;
+    void *const *tw = h->pristine;
+    s.Ps0 = (double *)tw[TW_Ps]; s.Rs0 = (double *)tw[TW_Rs]; s.Vs0 = (double *)tw[TW_Vs]; s.Bas0 = (double *)tw[TW_Bas]; s.Bgs0 = (double *)tw[TW_Bgs];
+    s.se30 = (isv_se3_prior_t *)tw[TW_se3]; s.lin90 = (isv_linear9_t *)tw[TW_lin9]; s.relpose0 = (isv_relpose_t *)tw[TW_relpose]; s.rollpitch0 = (isv_rollpitch_t *)tw[TW_rollpitch];
     q->enabled = 1;
     return ISV_OK;
 }
@@ -777,8 +778,8 @@ extern "C" int isv_backend_seq_frame(isv_backend_t *h, int32_t n, const isv_seq_
     // the extrinsic the kernels read is the caller's, every frame: k_finalize leaves R(q(ric)) in d.ric, the re-upload path
     // hands the pristine matrix over again
     if (!c.estimate_extrinsic) {       // (a free extrinsic is CARRIED from solve to solve: tic[0] / ric[0] of double2vector, round 4)
-        HIPCHK(h, hipMemcpyAsync(d.tic, h->tic0, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d.ric, h->ric0, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d.tic, h->pristine[TW_tic], sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d.ric, h->pristine[TW_ric], sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToDevice, st));
     }
     hipLaunchKernelGGL(k_seq_slide, dim3(n), dim3(256), 0, st, d, s);
     hipLaunchKernelGGL(k_seq_append, dim3(n), dim3(256), 0, st, d, s);
@@ -806,7 +807,7 @@ extern "C" int isv_backend_seq_frame(isv_backend_t *h, int32_t n, const isv_seq_
     HIPCHK(h, hipMemcpyAsync(q->h_out, s.out, sizeof(double) * (size_t)n * SEQ_OUT, hipMemcpyDeviceToHost, st));
     if (solve_flags && L) HIPCHK(h, hipMemcpyAsync(q->h_flags, d.solve_flag, sizeof(int32_t) * L, hipMemcpyDeviceToHost, st));
     std::vector<isv_summary_t> sums((size_t)n);
-    TRY(isv_solver_download(h->d, st, n, h->stage, sums.data(), any_marg ? marg : nullptr, h->err));      // (synchronises the stream)
+    TRY(isv_solver_download(h, n, sums.data(), any_marg ? marg : nullptr));      // (synchronises the stream)
     const auto t2 = std::chrono::steady_clock::now();
     h->resident = 0;                                      // (the batch API's restore copies do not describe this state)
     int rc = ISV_OK;
@@ -844,8 +845,8 @@ extern "C" int isv_backend_seq_flush(isv_backend_t *h, int32_t n, const int32_t 
     }
     HIPCHK(h, hipMemcpyAsync(s.f_hdr, q->h_hdr, sizeof(int32_t) * (size_t)n * SEQ_HDR, hipMemcpyHostToDevice, st));
     if (!h->cfg.estimate_extrinsic) {
-        HIPCHK(h, hipMemcpyAsync(h->d.tic, h->tic0, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(h->d.ric, h->ric0, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(h->d.tic, h->pristine[TW_tic], sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(h->d.ric, h->pristine[TW_ric], sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToDevice, st));
     }
     h->d.B = n;
     hipLaunchKernelGGL(k_seq_slide, dim3(n), dim3(256), 0, st, h->d, s);

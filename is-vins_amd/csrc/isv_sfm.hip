@@ -1019,7 +1019,7 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
     if (n_tr > INT32_MAX || n_obs > INT32_MAX || n_pts > INT32_MAX || n_poff > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
     // one upload block: [headers | tracks | obs | dv | sdt | pt_uv | pt_off | pt_trk]; then, device only: results, positions,
     // states (the three zeroed before the launch), the per-track blocks
-    InitLayout L;
+    BlockLayout L;
     const size_t o_hd = L.add(sizeof(SfmHdr) * n), o_tr = L.add(sizeof(isv_sfm_track_t) * (n_tr + 1)), o_obs = L.add(16 * (n_obs + 1));
     const size_t o_dv = L.add(24 * (n_fr + 1)), o_sdt = L.add(8 * (n_fr + 1)), o_uv = L.add(16 * (n_pts + 1)), o_poff = L.add(4 * (n_poff + 1));
     const size_t o_ptrk = L.add(4 * (n_pts + 1));

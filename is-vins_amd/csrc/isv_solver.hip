@@ -18,6 +18,7 @@
 #include "isv_proj_factor.h"
 #include "isv_prior_factor.h"
 #include "isv_imu_factor.h"
+#include "isv_batch_buffers.h"
 
 extern size_t build_solve_lds_bytes(int N);
 template <bool BIG, int NC, int MODE> __global__ void k_build_solve_sb(DevBatch d);
@@ -286,15 +287,13 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     TRYA(dal(&d.grad_l, L, allocs, err)); TRYA(dal(&d.gn_l, L, allocs, err)); TRYA(dal(&d.delta_l, L, allocs, err)); TRYA(dal(&d.lm_aterm, L, allocs, err));
     TRYA(dal(&d.fcost_c, F, allocs, err)); TRYA(dal(&d.imu_cost_c, NI, allocs, err)); TRYA(dal(&d.prior_cost_c, B * (size_t)d.n_prior_slots, allocs, err)); TRYA(dal(&d.cost_c, B, allocs, err));
     TRYA(dal(&d.fmodel, F, allocs, err)); TRYA(dal(&d.imu_model, NI, allocs, err)); TRYA(dal(&d.prior_model, B * (size_t)d.n_prior_slots, allocs, err)); TRYA(dal(&d.model, B, allocs, err));
-    TRYA(dal(&d.trace_cost, B * ISV_MAX_TRACE, allocs, err)); TRYA(dal(&d.trace_radius, B * ISV_MAX_TRACE, allocs, err));
-    TRYA(dal(&d.trace_step, B * ISV_MAX_TRACE, allocs, err)); TRYA(dal(&d.trace_acc, B * ISV_MAX_TRACE, allocs, err));
+    // (the traces, d.marg, d.margin_old, d.header0: transfer buffers, placed by the caller -- isv_batch_buffers.h)
     d.tvis_sz = 36 * (d.N * (d.N + 1) / 2) + 18 * d.N;
     TRYA(dal(&d.W, (F + L) * 6, allocs, err)); TRYA(dal(&d.lm_cg, L, allocs, err));
     d.wd_ld = 16 * ((6 * d.N + 16) / 16);          // 6N pose columns + the g_l column, rounded up to 16
     TRYA(dal(&d.Tvis, B * (size_t)d.tvis_sz, allocs, err));
     TRYA(dal(&d.dbg, B * 64, allocs, err)); TRYA(dal(&d.act, ISV_MAX_TRACE, allocs, err));
     HCHK(hipMemset(d.dbg, 0, B * 64 * sizeof(double)));
-    TRYA(dal(&d.marg, B, allocs, err)); TRYA(dal(&d.margin_old, B, allocs, err)); TRYA(dal(&d.header0, B, allocs, err));
     const size_t nblkT = (size_t)d.N * (d.N + 1) / 2 * 225;
     // LDS-resident fast path: the structure-aware solve (two windows per CU up to N = 11, one beyond), the pair
     // partials of k_sweep_mfma and the panel + landmark tables of k_rank1_mfma must fit the 160 KB of a CU
@@ -620,22 +619,14 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     return ISV_OK;
 }
 
-// staged: the caller has brought the records into g already (isv_batch_download's two-copy form) and synchronised
-int isv_solver_download(DevBatch &d, hipStream_t st, int n, const SolverStage &g, isv_summary_t *summary, isv_marg_result_t *marg, std::string &err, bool staged) {
+// the result records of n solved windows, array by array: the summaries' (if asked for), the marginalisation records (if asked for);
+// synchronises the handle's stream and unpacks them
+int isv_solver_download(isv_backend *h, int n, isv_summary_t *summary, isv_marg_result_t *marg) {
     if (!summary && !marg) return ISV_OK;
-    const size_t nt = (size_t)n * ISV_MAX_TRACE;
-    if (!staged) {
-    if (summary) {
-        HCHK(hipMemcpyAsync(g.st, d.st, sizeof(SolveState) * n, hipMemcpyDeviceToHost, st));
-        HCHK(hipMemcpyAsync(g.tc, d.trace_cost, sizeof(double) * nt, hipMemcpyDeviceToHost, st));
-        HCHK(hipMemcpyAsync(g.tr, d.trace_radius, sizeof(double) * nt, hipMemcpyDeviceToHost, st));
-        HCHK(hipMemcpyAsync(g.ts, d.trace_step, sizeof(double) * nt, hipMemcpyDeviceToHost, st));
-        HCHK(hipMemcpyAsync(g.ta, d.trace_acc, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-    }
-    if (marg) HCHK(hipMemcpyAsync(g.marg, d.marg, sizeof(isv_marg_result_t) * n, hipMemcpyDeviceToHost, st));
-    HCHK(hipStreamSynchronize(st));
-    }
-    for (int b = 0; b < n; b++) isv_solver_unpack_window(g, b, summary ? &summary[b] : nullptr, marg ? &marg[b] : nullptr);
+    std::string &err = h->err;
+    HCHK(copy_batch_buffers(h, BatchDims{(size_t)n, 0, 0, 0, 0}, (summary ? BUF_SUMMARY : 0u) | (marg ? BUF_MARG : 0u), 0, false));
+    HCHK(hipStreamSynchronize(h->stream));
+    for (int b = 0; b < n; b++) isv_solver_unpack_window(h->stage, b, summary ? &summary[b] : nullptr, marg ? &marg[b] : nullptr);
     return ISV_OK;
 }
 
