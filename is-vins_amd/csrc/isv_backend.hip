@@ -892,24 +892,29 @@ extern "C" int isv_batch_pack_results(isv_backend_t *h, void *device_dst, void *
     return ISV_OK;
 }
 
-// test hook: prior strips / per-block costs of window 0 after isv_backend_linearize
+// test hook: prior strips / per-block costs of window 0 after isv_backend_linearize, and the step vectors of the last solve
+// (isv_solver_debug_read).  `count` doubles; more than the handle allocated for the selected buffer is ISV_ERR_INVALID_ARG.
 extern "C" int isv_debug_read(isv_backend_t *h, int32_t what, double *out, int64_t count) {
     if (!h || !out) return ISV_ERR_INVALID_ARG;
     ENTER(h);
     DevBatch &d = h->d; hipStream_t st = h->stream;
     const double *src = nullptr;
+    const size_t B = h->capB, NI = B * (size_t)(d.N - 1);
+    size_t cap = 0;
     switch (what) {
-    case 0: src = d.prior_strip; break;
-    case 1: src = d.prior_cost; break;
-    case 2: src = d.imu_sqrt; break;
-    case 3: src = d.fcost; break;
-    case 4: src = d.imu_cost; break;
-    case 5: src = d.pose; break;
-    case 6: src = d.lam; break;
-    case 7: src = d.cost; break;
-    case 22: src = d.strip_ex; if (!src) return ISV_ERR_INVALID_ARG; break;
-    default: return isv_solver_debug_read(h->d, st, what, out, count, h->err);
+    case 0: src = d.prior_strip; cap = B * (size_t)d.prior_strip_sz; break;
+    case 1: src = d.prior_cost; cap = B * (size_t)d.n_prior_slots; break;
+    case 2: src = d.imu_sqrt; cap = NI * 225; break;
+    case 3: src = d.fcost; cap = h->capF; break;
+    case 4: src = d.imu_cost; cap = NI; break;
+    case 5: src = d.pose; cap = B * (size_t)d.N * 7; break;
+    case 6: src = d.lam; cap = h->capL; break;
+    case 7: src = d.cost; cap = B; break;
+    case 22: src = d.strip_ex; cap = h->capF * 12; if (!src) return ISV_ERR_INVALID_ARG; break;
+    default: return isv_solver_debug_read(h->d, st, what, out, count, h->capB, h->capL, h->err);
     }
+    if (count < 0 || (size_t)count > cap) { h->err = "isv_debug_read: count exceeds the buffer"; return ISV_ERR_INVALID_ARG; }
+    if (count == 0) return ISV_OK;
     D2H(out, src, count);
     HIPCHK(h, hipStreamSynchronize(st));
     return ISV_OK;

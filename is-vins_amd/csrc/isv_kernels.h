@@ -59,6 +59,7 @@ struct SolverHost {
     bool no_update = false;           // ISV_DEBUG_NO_UPDATE (sensitivity study, tests/test_sequence_long.py; the oracle has the same
                                       // hook): skip the update() of the prior factors' pseudo-measurements after the solve
                                       // (src/estimator.cpp:1133-1144).  NOT the reference's behaviour.
+    bool debug_path = false;          // ISV_DEBUG_PATH (read at create): stderr lines naming the handle's and every enqueue's kernel choices (tests assert them)
     SolverKernel kern[KR_COUNT];      // the kernel of each role on this handle
 };
 int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, std::vector<void *> &allocs, std::string &err);
@@ -95,4 +96,4 @@ size_t upload_build_lds_bytes(int N, int lcap);
 int isv_upload_build_enqueue(DevBatch &d, const int32_t *optr, const double *obs_raw, int lcap, hipStream_t st);
 int isv_solver_download(struct isv_backend *h, int n, isv_summary_t *summary, isv_marg_result_t *marg);
 void isv_solver_unpack_window(const SolverStage &stage, int b, isv_summary_t *summary, isv_marg_result_t *marg);
-int isv_solver_debug_read(DevBatch &d, hipStream_t st, int what, double *out, int64_t count, std::string &err);
+int isv_solver_debug_read(DevBatch &d, hipStream_t st, int what, double *out, int64_t count, size_t capB, size_t capL, std::string &err);

@@ -416,6 +416,11 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
             }
         }
     }
+    hc.debug_path = getenv("ISV_DEBUG_PATH") != nullptr;
+    if (hc.debug_path)
+        fprintf(stderr, "isv: handle chain_split=%d generic_n=%d no_pose_dogleg=%d lg_batch_waves=%d split_control=%d legacy_visual=%d pose_dogleg_kernel=%d r1_in_lg_kernel=%d split_cap=%d\n",
+                (int)hc.chain_split, (int)hc.generic_n, (int)hc.no_pose_dogleg, (int)hc.lg_batch_waves, (int)hc.split_control, (int)hc.legacy_visual,
+                k[KR_POSE_DOGLEG].fn ? 1 : 0, k[KR_LIN_GRAM_CHAIN_R1].fn ? 1 : 0, (int)d.split_cap);
     for (const SolverKernel &e : hc.kern) HCHK(isv_raise_dynamic_lds(e.fn, dev0_, e.lds));
     // device figures the per-launch variant choice needs (once per handle, not per isv_batch_optimize): hc.n_cus (above) and the
     // workgroups of k_dogleg<true, EX> per CU by registers alone (a small dynamic LDS request); the LDS bound is applied per enqueue
@@ -490,6 +495,9 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     // (+ the 2 KB of static reduction space)
     const size_t lds_pd = K[KR_POSE].lds > lds_dgc ? K[KR_POSE].lds : lds_dgc;
     const bool pose_dogleg = K[KR_POSE_DOGLEG].fn && fuse_control && !bsub_split && lds_pd + 2304 <= ISV_LDS_PER_CU;
+    if (hc.debug_path)
+        fprintf(stderr, "isv: enqueue B=%d lg_lcap=%d fused=%d lgw=%d lg_chain=%d r1_in_lg=%d split=%d bsub_split=%d fuse_control=%d pose_dogleg=%d\n",
+                d.B, d.lg_lcap, (int)fused, lgw, (int)lg_chain, (int)r1_in_lg, (int)split, (int)bsub_split, (int)fuse_control, (int)pose_dogleg);
     hipLaunchKernelGGL(k_init_state, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
     for (int slot = 0; slot < d.max_iter; slot++) {
         // linearise where needed (k_*_linearize skip windows whose need_linearize == 0 via the tile/window flags)
@@ -646,23 +654,30 @@ void isv_solver_unpack_window(const SolverStage &g, int b, isv_summary_t *summar
     }
 }
 
-int isv_solver_debug_read(DevBatch &d, hipStream_t st, int what, double *out, int64_t count, std::string &err) {
+// test hook: the step vectors of the last enqueue.  `count` is bounded by what the handle allocated (capB windows, capL landmarks):
+// a wrong count from a test is an error, not a read past the buffer
+int isv_solver_debug_read(DevBatch &d, hipStream_t st, int what, double *out, int64_t count, size_t capB, size_t capL, std::string &err) {
     const double *src = nullptr;
+    const size_t per_p = capB * (size_t)d.np;
+    size_t cap = 0;
     switch (what) {
-    case 10: src = d.gn_p; break;
-    case 11: src = d.gn_l; break;
-    case 12: src = d.grad_p; break;
-    case 13: src = d.grad_l; break;
-    case 14: src = d.scale_p; break;
-    case 15: src = d.scale_l; break;
-    case 16: src = d.diag_p; break;
-    case 17: src = d.delta_p; break;
-    case 18: src = d.delta_l; break;
-    case 19: src = d.cost_c; break;
-    case 20: src = d.model; break;
-    case 21: src = d.dbg; break;
+    case 10: src = d.gn_p; cap = per_p; break;
+    case 11: src = d.gn_l; cap = capL; break;
+    case 12: src = d.grad_p; cap = per_p; break;
+    case 13: src = d.grad_l; cap = capL; break;
+    case 14: src = d.scale_p; cap = per_p; break;
+    case 15: src = d.scale_l; cap = capL; break;
+    case 16: src = d.diag_p; cap = per_p; break;
+    case 17: src = d.delta_p; cap = per_p; break;
+    case 18: src = d.delta_l; cap = capL; break;
+    case 19: src = d.cost_c; cap = capB; break;
+    case 20: src = d.model; cap = capB; break;
+    case 21: src = d.dbg; cap = capB * 64; break;
+    case 23: src = d.diag_l; cap = capL; break;
     default: return ISV_ERR_INVALID_ARG;
     }
+    if (count < 0 || (size_t)count > cap) { err = "isv_debug_read: count exceeds the buffer"; return ISV_ERR_INVALID_ARG; }
+    if (count == 0) return ISV_OK;
     HCHK(hipMemcpyAsync(out, src, sizeof(double) * count, hipMemcpyDeviceToHost, st));
     HCHK(hipStreamSynchronize(st));
     return ISV_OK;
