@@ -307,6 +307,33 @@ struct isv_estimator {
 
 namespace {
 
+using clk = std::chrono::steady_clock;
+double ms(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+// when solve_windows had set up, triangulated, run the first solves' initFactorGraph, and solved: the ends of step_ms[1..4]
+struct SolveStamps { clk::time_point set_up, triangulated, initialised, solved; };
+
+// frame i's five states (Ps, Rs, Vs, Bas, Bgs) out to raw arrays of 3 / 9 / 3 / 3 / 3 doubles, and back
+void store_frame(const Sequence &s, int i, double *P, double *R, double *V, double *Ba, double *Bg) {
+    std::memcpy(P, s.Ps[i].data(), 24); std::memcpy(R, s.Rs[i].data(), 72); std::memcpy(V, s.Vs[i].data(), 24);
+    std::memcpy(Ba, s.Bas[i].data(), 24); std::memcpy(Bg, s.Bgs[i].data(), 24);
+}
+void load_frame(Sequence &s, int i, const double *P, const double *R, const double *V, const double *Ba, const double *Bg) {
+    std::memcpy(s.Ps[i].data(), P, 24); std::memcpy(s.Rs[i].data(), R, 72); std::memcpy(s.Vs[i].data(), V, 24);
+    std::memcpy(s.Bas[i].data(), Ba, 24); std::memcpy(s.Bgs[i].data(), Bg, 24);
+}
+// slideWindow's per-frame move: the five states and the header of frame `src` into frame `dst`
+void copy_frame(Sequence &s, int dst, int src) {
+    s.Ps[dst] = s.Ps[src]; s.Rs[dst] = s.Rs[src]; s.Vs[dst] = s.Vs[src]; s.Bas[dst] = s.Bas[src]; s.Bgs[dst] = s.Bgs[src]; s.Headers[dst] = s.Headers[src];
+}
+// size the window buffers of the states and prior factors (n_rp roll/pitch slots); bind them, the two priors and the extrinsic into w
+void bind_window(Sequence &s, isv_window_t &w, size_t n_rp) {
+    s.wPs.resize(s.N * 3); s.wRs.resize(s.N * 9); s.wVs.resize(s.N * 3); s.wBas.resize(s.N * 3); s.wBgs.resize(s.N * 3);
+    s.wrel.resize(s.Nvo - 1); s.wrp.resize(n_rp);
+    w.Ps = s.wPs.data(); w.Rs = s.wRs.data(); w.Vs = s.wVs.data(); w.Bas = s.wBas.data(); w.Bgs = s.wBgs.data();
+    w.tic = s.wtic; w.ric = s.wric;
+    w.pose_prior = &s.wpp; w.vb_prior = &s.wvb; w.relpose = s.wrel.data(); w.rollpitch = s.wrp.data();
+}
+
 // Utility::deltaQ(theta).toRotationMatrix(): q = [1, theta / 2], not normalised
 M3 delta_q_matrix(const V3 &theta) { return qmat(Quat{1.0, theta[0] / 2, theta[1] / 2, theta[2] / 2}); }
 
@@ -340,8 +367,7 @@ bool add_features(Sequence &s, double min_parallax, bool record = false) {
         }
     }
     if (fc < 2 || last_track_num < 20) return true;
-    double parallax_sum = 0;
-    int parallax_num = 0;
+    double parallax_sum = 0; int parallax_num = 0;
     for (const Track &t : s.tracks) {
         if (t.start_frame <= fc - 2 && t.end_frame() >= fc - 1) {
             const V3 &pi = s.pt(t, fc - 2 - t.start_frame), &pj = s.pt(t, fc - 1 - t.start_frame);
@@ -354,21 +380,25 @@ bool add_features(Sequence &s, double min_parallax, bool record = false) {
     return parallax_sum / parallax_num >= min_parallax;
 }
 
-// the Estimator members backendOptimization() touches, as an isv_window_t over this sequence's buffers
-int build_window(const isv_estimator *e, Sequence &s, std::string &err) {
-    const int N = s.N, Nvo = s.Nvo;
+// goodFeature(): used_num >= 2 && start_frame < Vo_SIZE.  Fills s.good (indices into tracks, list order); returns their observations
+size_t select_good(Sequence &s) {
     s.good.clear();
     size_t n_obs = 0;
-    for (size_t i = 0; i < s.tracks.size(); i++)            // goodFeature(): used_num >= 2 && start_frame < Vo_SIZE
-        if (s.tracks[i].n >= 2 && s.tracks[i].start_frame < Nvo) { s.good.push_back((int)i); n_obs += (size_t)s.tracks[i].n; }
-    const size_t L = s.good.size();
+    for (size_t i = 0; i < s.tracks.size(); i++)
+        if (s.tracks[i].n >= 2 && s.tracks[i].start_frame < s.Nvo) { s.good.push_back((int)i); n_obs += (size_t)s.tracks[i].n; }
+    return n_obs;
+}
+
+// the Estimator members backendOptimization() touches, as an isv_window_t over this sequence's buffers
+int build_window(const isv_estimator *e, Sequence &s, std::string &err) {
+    const int N = s.N;
+    const size_t n_obs = select_good(s), L = s.good.size();
     if ((int)L > e->p.cfg.max_landmarks || (int)n_obs > e->p.cfg.max_obs) { err = "window exceeds the landmark / observation capacity"; return ISV_ERR_CAPACITY; }
     if ((int)s.rollpitch.size() > e->p.cfg.max_rollpitch) { err = "more roll/pitch factors than max_rollpitch"; return ISV_ERR_CAPACITY; }
-    s.wPs.resize(N * 3); s.wRs.resize(N * 9); s.wVs.resize(N * 3); s.wBas.resize(N * 3); s.wBgs.resize(N * 3);
-    for (int i = 0; i < N; i++) {
-        std::memcpy(&s.wPs[i * 3], s.Ps[i].data(), 24); std::memcpy(&s.wRs[i * 9], s.Rs[i].data(), 72); std::memcpy(&s.wVs[i * 3], s.Vs[i].data(), 24);
-        std::memcpy(&s.wBas[i * 3], s.Bas[i].data(), 24); std::memcpy(&s.wBgs[i * 3], s.Bgs[i].data(), 24);
-    }
+    isv_window_t &w = s.w;
+    s.wpp = s.pose_prior; s.wvb = s.vb_prior; s.wrel = s.relpose; s.wrp = s.rollpitch;
+    bind_window(s, w, std::max<size_t>(s.rollpitch.size(), 1));
+    for (int i = 0; i < N; i++) store_frame(s, i, &s.wPs[i * 3], &s.wRs[i * 9], &s.wVs[i * 3], &s.wBas[i * 3], &s.wBgs[i * 3]);
     // estimate_extrinsic = 0: the configured extrinsic, every frame (a constant parameter block; the reference's double2vector
     // round-trips it through a quaternion each frame, a rounding-level drift this port does not reproduce).  = 1: what the
     // previous solve left in tic[0] / ric[0] (double2vector, src/estimator.cpp:575-583), the configured one before the first solve.
@@ -389,19 +419,11 @@ int build_window(const isv_estimator *e, Sequence &s, std::string &err) {
         if (!s.pre[j]) { err = "a window frame has no pre-integration (no IMU samples were fed)"; return ISV_ERR_INVALID_ARG; }
         s.wimu[j - 1] = s.pre[j]->pod;
     }
-    s.wpp = s.pose_prior; s.wvb = s.vb_prior;
-    s.wrel = s.relpose;
-    s.wrp = s.rollpitch;
-    if (s.wrp.empty()) s.wrp.resize(1);
     s.wpose.assign(N * 7, 0.0); s.wsb.assign(N * 9, 0.0); s.wex.assign(7, 0.0);
-    isv_window_t &w = s.w;
-    w.Ps = s.wPs.data(); w.Rs = s.wRs.data(); w.Vs = s.wVs.data(); w.Bas = s.wBas.data(); w.Bgs = s.wBgs.data();
-    w.tic = s.wtic; w.ric = s.wric;
     w.n_landmarks = (int32_t)L; w.n_obs = (int32_t)n_obs;
     w.lm_start_frame = s.wstart.data(); w.lm_obs_ptr = s.wptr.data(); w.obs_point = s.wobs.data();
     w.lm_depth = s.wdepth.data(); w.lm_solve_flag = s.wflag.data();
     w.imu = s.wimu.data();
-    w.pose_prior = &s.wpp; w.vb_prior = &s.wvb; w.relpose = s.wrel.data(); w.rollpitch = s.wrp.data();
     w.n_rollpitch = (int32_t)s.rollpitch.size();
     w.margin_old = s.margin_old ? 1 : 0;
     w.header0 = s.Headers[0];
@@ -411,11 +433,7 @@ int build_window(const isv_estimator *e, Sequence &s, std::string &err) {
 
 // what double2vector() and update() leave in the Estimator members
 void read_back(Sequence &s) {
-    const int N = s.N;
-    for (int i = 0; i < N; i++) {
-        std::memcpy(s.Ps[i].data(), &s.wPs[i * 3], 24); std::memcpy(s.Rs[i].data(), &s.wRs[i * 9], 72); std::memcpy(s.Vs[i].data(), &s.wVs[i * 3], 24);
-        std::memcpy(s.Bas[i].data(), &s.wBas[i * 3], 24); std::memcpy(s.Bgs[i].data(), &s.wBgs[i * 3], 24);
-    }
+    for (int i = 0; i < s.N; i++) load_frame(s, i, &s.wPs[i * 3], &s.wRs[i * 9], &s.wVs[i * 3], &s.wBas[i * 3], &s.wBgs[i * 3]);
     for (size_t l = 0; l < s.good.size(); l++) { Track &t = s.tracks[s.good[l]]; t.depth = s.wdepth[l]; t.solve_flag = s.wflag[l]; }
     s.pose_prior = s.wpp; s.vb_prior = s.wvb;
     s.relpose = s.wrel;
@@ -430,19 +448,12 @@ void new_preintegration(const isv_estimator *e, Sequence &s, int j) {
 // Estimator::slideWindow  src/estimator.cpp:1565-1724
 void slide_window(const isv_estimator *e, Sequence &s) {
     const int N = s.N, Nvo = s.Nvo;
+    if (s.frame_count != N - 1) return;
     if (s.margin_old) {
         const M3 back_R0 = s.Rs[0];
         const V3 back_P0 = s.Ps[0];
-        if (s.frame_count != N - 1) return;
-        for (int i = 0; i < N - 1; i++) {
-            std::swap(s.Ps[i], s.Ps[i + 1]); std::swap(s.Rs[i], s.Rs[i + 1]); std::swap(s.Vs[i], s.Vs[i + 1]);
-            std::swap(s.Bas[i], s.Bas[i + 1]); std::swap(s.Bgs[i], s.Bgs[i + 1]); std::swap(s.Headers[i], s.Headers[i + 1]);
-            std::swap(s.pre[i], s.pre[i + 1]); std::swap(s.bufs[i], s.bufs[i + 1]);
-        }
-        s.Headers[N - 1] = s.Headers[N - 2];
-        s.Ps[N - 1] = s.Ps[N - 2]; s.Rs[N - 1] = s.Rs[N - 2]; s.Vs[N - 1] = s.Vs[N - 2]; s.Bas[N - 1] = s.Bas[N - 2]; s.Bgs[N - 1] = s.Bgs[N - 2];
-        new_preintegration(e, s, N - 1);
-        s.bufs[N - 1].clear();
+        // (the reference swaps the frames down, then copies N-2 over N-1: the newest states and header stay where they are)
+        for (int i = 0; i < N - 1; i++) { copy_frame(s, i, i + 1); std::swap(s.pre[i], s.pre[i + 1]); std::swap(s.bufs[i], s.bufs[i + 1]); }
         const bool shift_depth = s.flag == NON_LINEAR;
         if (shift_depth && s.have_to_add) {            // the prior factors move one frame towards the past (:1607-1645)
             for (auto &f : s.relpose) { f.imu_i -= 1; f.imu_j -= 1; }                  // RelativePoseFactor::shift()
@@ -484,15 +495,11 @@ void slide_window(const isv_estimator *e, Sequence &s) {
         }
     } else {
         const int fc = s.frame_count;
-        if (fc != N - 1) return;
         for (const Sample &smp : s.bufs[fc]) {
             s.pre[fc - 1]->push_back(smp.dt, smp.acc, smp.gyr);
             s.bufs[fc - 1].push_back(smp);
         }
-        s.Headers[fc - 1] = s.Headers[fc];
-        s.Ps[fc - 1] = s.Ps[fc]; s.Rs[fc - 1] = s.Rs[fc]; s.Vs[fc - 1] = s.Vs[fc]; s.Bas[fc - 1] = s.Bas[fc]; s.Bgs[fc - 1] = s.Bgs[fc];
-        new_preintegration(e, s, N - 1);
-        s.bufs[N - 1].clear();
+        copy_frame(s, fc - 1, fc);
         s.compact([&](Track &t) {                      // slideWindowNew -> removeFront  :335-354
             if (t.start_frame == fc) { t.start_frame--; return true; }
             if (t.end_frame() < fc - 1) return true;
@@ -500,18 +507,42 @@ void slide_window(const isv_estimator *e, Sequence &s) {
             return t.n > 0;
         });
     }
+    new_preintegration(e, s, N - 1);
+    s.bufs[N - 1].clear();
 }
 
-void after_solve(const isv_estimator *e, Sequence &s, double header) {
+// the staged image into the track lists and its header into the window (record: with the frame's observations kept for the device)
+void take_image(const isv_estimator *e, Sequence &s, bool record) {
+    s.margin_old = add_features(s, e->p.min_parallax, record);
+    s.Headers[s.frame_count] = s.staged_header;
+    s.staged = false;
+}
+
+// valid marginalisation outputs wait for the slide (MargForward / MargBackward  src/estimator.cpp:1536-1538)
+void install_marg(Sequence &s, const isv_marg_result_t &m) {
+    if (!m.valid) return;
+    s.add_pose_prior = m.forward_pose_prior; s.add_relpose = m.backward_relpose; s.add_vb = m.backward_vb; s.have_to_add = true;
+    isv_rollpitch_t brp = m.backward_rollpitch; brp.index = s.Nvo - 1;
+    s.rollpitch.push_back(brp);                     // vioRollPitchEdges.push_back
+}
+
+// The end of one sequence's solve on either path: the failed-solve policy, the counters, the slide, the trajectory rows.  A solve with a
+// non-finite cost (ok = false) was not copied into the window (the reference has no such guard: its NaNs would spread through every later
+// frame): the sequence keeps its states and depths, drops this frame's marginalisation outputs, and the failure is counted.  The window
+// still slides (as NON_LINEAR: removeBackShiftDepth re-hosts the depths), but without those outputs the priors cannot follow it, so AFTER
+// the slide the sequence goes back to INITIAL_STRUCTURE: its next solve rebuilds every prior through initFactorGraph (:1543-1548).
+void finish_solve(const isv_estimator *e, Sequence &s, const isv_summary_t &summary, bool ok) {
+    if (!ok) { s.n_failed++; s.have_to_add = false; }
+    s.last_summary = summary; s.n_solves++; s.n_good_last = (int)s.good.size();
+    std::array<double, 13> nr;
+    nr[0] = s.Headers[s.N - 1];
     slide_window(e, s);
     s.compact([](Track &t) { return t.solve_flag != 2; });      // removeFailures
-    const int N = s.N;
-    std::array<double, 13> nr;
-    nr[0] = header;
-    std::memcpy(&nr[1], s.Ps[N - 1].data(), 24); std::memcpy(&nr[4], s.Rs[N - 1].data(), 72);
+    std::memcpy(&nr[1], s.Ps[s.N - 1].data(), 24); std::memcpy(&nr[4], s.Rs[s.N - 1].data(), 72);
     s.newest_rows.push_back(nr);
     const Quat q = quat_of(s.Rs[0]);
     s.pose_rows.push_back({s.Headers[0], s.Ps[0][0], s.Ps[0][1], s.Ps[0][2], q.w, q.x, q.y, q.z});
+    if (!ok) { s.flag = INITIAL_STRUCTURE; s.rollpitch.clear(); }
 }
 
 // run body(i) for i in [0, n) on min(8, cores) host threads (ISV_HOST_THREADS overrides), one per >= 8 items; the
@@ -701,7 +732,7 @@ int seed_resident(isv_estimator *e) {
         if ((int)s.tracks.size() > e->tracks_cap) return ISV_ERR_CAPACITY;
         std::string err;
         const int rc = build_window(e, s, err);
-        if (rc != ISV_OK) { e->err = err; return rc; }
+        if (rc != ISV_OK) return rc;
         ws[si] = &s.w;
         nt[si] = (int32_t)s.tracks.size();
         trk[si].resize(s.tracks.size());
@@ -741,23 +772,15 @@ int leave_resident(isv_estimator *e, bool host_has_slid, bool pre_add = false, c
     for (size_t si = 0; si < e->seq.size(); si++) {
         Sequence &s = e->seq[si];
         if (!s.resident) continue;
-        const int N = s.N;
-        s.wPs.resize(N * 3); s.wRs.resize(N * 9); s.wVs.resize(N * 3); s.wBas.resize(N * 3); s.wBgs.resize(N * 3);
-        s.wrel.resize(s.Nvo - 1); s.wrp.resize(std::max(1, e->p.cfg.max_rollpitch));
         isv_window_t w{};
-        w.Ps = s.wPs.data(); w.Rs = s.wRs.data(); w.Vs = s.wVs.data(); w.Bas = s.wBas.data(); w.Bgs = s.wBgs.data();
-        w.pose_prior = &s.wpp; w.vb_prior = &s.wvb; w.relpose = s.wrel.data(); w.rollpitch = s.wrp.data();
-        w.tic = s.wtic; w.ric = s.wric;
+        bind_window(s, w, (size_t)std::max(1, e->p.cfg.max_rollpitch));
         const size_t ntr = ntracks(s);
         std::vector<double> dep(std::max<size_t>(ntr, 1));
         std::vector<int32_t> fl(std::max<size_t>(ntr, 1));
         const int rc = isv_backend_seq_download(e->backend, (int32_t)si, &w, (int32_t)ntr, dep.data(), fl.data());
         if (rc != ISV_OK) { e->err = std::string("leaving the resident mode failed: ") + isv_backend_last_error(e->backend); return rc; }
         // (after a slide the newest frame is the host's: processIMU may already have propagated it with the next frame's samples)
-        for (int i = 0; i < (has_slid(si) ? N - 1 : N); i++) {
-            std::memcpy(s.Ps[i].data(), &s.wPs[i * 3], 24); std::memcpy(s.Rs[i].data(), &s.wRs[i * 9], 72); std::memcpy(s.Vs[i].data(), &s.wVs[i * 3], 24);
-            std::memcpy(s.Bas[i].data(), &s.wBas[i * 3], 24); std::memcpy(s.Bgs[i].data(), &s.wBgs[i * 3], 24);
-        }
+        for (int i = 0; i < (has_slid(si) ? s.N - 1 : s.N); i++) load_frame(s, i, &s.wPs[i * 3], &s.wRs[i * 9], &s.wVs[i * 3], &s.wBas[i * 3], &s.wBgs[i * 3]);
         if (e->p.cfg.estimate_extrinsic) { std::memcpy(s.cur_tic, s.wtic, 24); std::memcpy(s.cur_ric, s.wric, 72); s.have_ex = true; }     // (tic[0] / ric[0])
         s.pose_prior = s.wpp; s.vb_prior = s.wvb; s.relpose = s.wrel;
         s.rollpitch.assign(s.wrp.begin(), s.wrp.begin() + w.n_rollpitch);
@@ -768,122 +791,118 @@ int leave_resident(isv_estimator *e, bool host_has_slid, bool pre_add = false, c
     return ISV_OK;
 }
 
-#define RESIDENT_FELL_BACK (-1000)      // resident_frame: the frame did not fit the resident path; the windows are back on the host
-// one lock-step frame of the resident sequences: only what is new crosses PCIe (include/isvins_backend.h)
-int resident_frame(isv_estimator *e, std::vector<std::string> &errs) {
+// The phases of resident_frame.  The pre-check: what can REFUSE the frame, for every sequence before any is touched.  Mutates nothing.
+int resident_precheck(isv_estimator *e) {
+    for (const Sequence &s : e->seq)
+        if (s.staged && (!s.pre[s.N - 1] || (s.last_slide == 2 && !s.pre[s.N - 2]))) { e->err = "a window frame has no pre-integration (no IMU samples were fed)"; return ISV_ERR_INVALID_ARG; }
+    return ISV_OK;
+}
+
+// Preparation of one sequence's hand-over record.  Refuses nothing: false = the frame does not fit (the re-upload path will solve it).
+// Mutates the sequence: tracks_before remembers the list the device holds, then the features go in.  Without an image it idles.
+bool prepare_frame(const isv_estimator *e, Sequence &s, isv_seq_frame_t &f) {
+    const int N = s.N;
+    std::memset(&f, 0, sizeof(f));
+    f.n_tracks = (int32_t)s.tracks.size();
+    s.tracks_before = (int)s.tracks.size();
+    if (!s.staged) { f.prev_slide = -1; return true; }
+    f.prev_slide = s.last_slide;
+    take_image(e, s, true);
+    s.features_added = true;
+    bool fits = (int)s.tracks.size() <= e->tracks_cap;
+    f.margin_old = s.margin_old ? 1 : 0;
+    f.n_obs = (int32_t)s.frame_obs.size(); f.obs = s.frame_obs.data();
+    for (const isv_seq_obs_t &o : s.frame_obs) if (o.slot >= e->tracks_cap) fits = false;
+    if (s.last_slide == 2) { s.frame_imu[0] = s.pre[N - 2]->pod; s.frame_imu[1] = s.pre[N - 1]->pod; f.n_imu = 2; }
+    else { s.frame_imu[0] = s.pre[N - 1]->pod; f.n_imu = 1; }
+    f.imu = s.frame_imu;
+    store_frame(s, N - 1, f.Ps, f.Rs, f.Vs, f.Bas, f.Bgs);
+    f.header0 = s.Headers[0];
+    const int64_t n_obs = (int64_t)select_good(s);
+    f.n_landmarks = (int32_t)s.good.size(); f.n_factors = (int32_t)(n_obs - (int64_t)s.good.size());
+    if (f.n_landmarks > e->p.cfg.max_landmarks || n_obs > e->p.cfg.max_obs) fits = false;
+    s.frame_flags.assign(std::max<size_t>(s.good.size(), 1), 0);
+    return fits;
+}
+
+// The fit decision.  Refuses nothing; mutates only the once-only ISV_DEBUG_SEQ_UNSUPPORTED_FRAME hook.
+bool frame_fits(isv_estimator *e, const std::vector<char> &fits) {
+    bool fit_all = true;
+    for (char f : fits) fit_all &= f != 0;
+    if (!e->dbg_unsupported_fired && e->resident_frames == e->dbg_unsupported_frame) { fit_all = false; e->dbg_unsupported_fired = true; }
+    return fit_all;
+}
+
+// Failed-frame recovery (a non-finite solve).  Refuses what the backend refuses.  Every window comes back to the host, not yet slid (an idle
+// one's pending slide is applied first); the sequences that did solve install their marginalisation outputs.  Serial: e->err is shared.
+int recover_failed_frame(isv_estimator *e, const std::vector<char> &idle, const std::vector<isv_seq_result_t> &res) {
+    int rc = leave_resident(e, false, false, &idle);
+    if (rc != ISV_OK) return rc;
+    for (size_t si = 0; si < e->seq.size(); si++) {
+        Sequence &s = e->seq[si];
+        isv_marg_result_t m;
+        if (idle[si] || res[si].summary.status != ISV_OK || !s.margin_old) continue;
+        rc = isv_backend_seq_marg(e->backend, (int32_t)si, &m);
+        if (rc != ISV_OK) { e->err = isv_backend_last_error(e->backend); return rc; }
+        install_marg(s, m);
+    }
+    return ISV_OK;
+}
+
+// Read-back and slide of one solved sequence; mutates only it.  Unless the whole window came back, its frames come from the result.
+void finish_resident(const isv_estimator *e, Sequence &s, const isv_seq_result_t &r, bool whole_window_back) {
+    if (!whole_window_back) {
+        load_frame(s, s.N - 1, r.Ps_new, r.Rs_new, r.Vs_new, r.Bas_new, r.Bgs_new);      // newest (processIMU); oldest and second (pose_output.txt rows)
+        std::memcpy(s.Ps[0].data(), r.Ps_old, 24); std::memcpy(s.Rs[0].data(), r.Rs_old, 72);
+        std::memcpy(s.Ps[1].data(), r.Ps_second, 24); std::memcpy(s.Rs[1].data(), r.Rs_second, 72);
+        for (size_t l = 0; l < s.good.size(); l++) s.tracks[s.good[l]].solve_flag = s.frame_flags[l];
+        if (e->p.cfg.estimate_extrinsic) { std::memcpy(s.cur_tic, r.tic, 24); std::memcpy(s.cur_ric, r.ric, 72); s.have_ex = true; }
+    }
+    finish_solve(e, s, r.summary, r.summary.status == ISV_OK);
+    s.last_slide = s.margin_old ? 1 : 2;
+}
+
+// One lock-step frame of the resident sequences.  Returns the sequences that solved, or an error.  fell_back: the frame did not fit, the
+// windows are back on the host with this frame's features in.  step_ms[1] preparation, [4] hand-over + device, [5] read-back + slide.
+int resident_frame(isv_estimator *e, std::vector<std::string> &errs, bool &fell_back) {
     const int S = (int)e->seq.size();
-    const auto tr0 = std::chrono::steady_clock::now();
+    const auto tr0 = clk::now();
     std::vector<isv_seq_frame_t> fr(S);
     std::vector<isv_seq_result_t> res(S);
     std::vector<int32_t *> flags(S);
     std::vector<char> fits(S, 1), idle(S, 0);
-    //  what can REFUSE the frame is checked for every sequence before any of them is touched: an error return must not
-    // leave some sequences with this image's features in their track lists and the device without them
-    for (const Sequence &s : e->seq)
-        if (s.staged && (!s.pre[s.N - 1] || (s.last_slide == 2 && !s.pre[s.N - 2]))) { e->err = "a window frame has no pre-integration (no IMU samples were fed)"; return ISV_ERR_INVALID_ARG; }
-    int rc = parallel_for(S, errs, [&](int si, std::string &err) {
+    int rc = resident_precheck(e);
+    if (rc != ISV_OK) return rc;
+    (void)parallel_for(S, errs, [&](int si, std::string &) {
         Sequence &s = e->seq[si];
-        const int N = s.N;
-        isv_seq_frame_t &f = fr[si];
-        std::memset(&f, 0, sizeof(f));
-        if (!s.staged) {                           // no image for this sequence this step (round 4): it idles on the device, its slide stays pending
-            f.prev_slide = -1; f.n_tracks = (int32_t)s.tracks.size();
-            s.tracks_before = (int)s.tracks.size();
-            idle[si] = 1; flags[si] = nullptr;
-            return (int)ISV_OK;
-        }
-        f.prev_slide = s.last_slide;
-        f.n_tracks = (int32_t)s.tracks.size();
-        // (from here on the host state changes.  A window that does not fit the resident store or the per-window
-        //  kernels is NOT an error -- the re-upload path solves it -- so the limits only mark the frame for the fall-back below;
-        //  the tracks this call appends are remembered so that the device's shorter list can be brought back consistently)
-        s.tracks_before = (int)s.tracks.size();
-        s.margin_old = add_features(s, e->p.min_parallax, true);
-        s.Headers[s.frame_count] = s.staged_header;
-        s.staged = false; s.features_added = true;
-        if ((int)s.tracks.size() > e->tracks_cap) fits[si] = 0;
-        f.margin_old = s.margin_old ? 1 : 0;
-        f.n_obs = (int32_t)s.frame_obs.size(); f.obs = s.frame_obs.data();
-        for (const isv_seq_obs_t &o : s.frame_obs) if (o.slot >= e->tracks_cap) fits[si] = 0;
-        if (s.last_slide == 2) { s.frame_imu[0] = s.pre[N - 2]->pod; s.frame_imu[1] = s.pre[N - 1]->pod; f.n_imu = 2; }
-        else { s.frame_imu[0] = s.pre[N - 1]->pod; f.n_imu = 1; }
-        f.imu = s.frame_imu;
-        std::memcpy(f.Ps, s.Ps[N - 1].data(), 24); std::memcpy(f.Rs, s.Rs[N - 1].data(), 72); std::memcpy(f.Vs, s.Vs[N - 1].data(), 24);
-        std::memcpy(f.Bas, s.Bas[N - 1].data(), 24); std::memcpy(f.Bgs, s.Bgs[N - 1].data(), 24);
-        f.header0 = s.Headers[0];
-        s.good.clear();
-        int64_t n_obs = 0;
-        for (size_t i = 0; i < s.tracks.size(); i++)
-            if (s.tracks[i].n >= 2 && s.tracks[i].start_frame < s.Nvo) { s.good.push_back((int)i); n_obs += s.tracks[i].n; }
-        f.n_landmarks = (int32_t)s.good.size(); f.n_factors = (int32_t)(n_obs - (int64_t)s.good.size());
-        if (f.n_landmarks > e->p.cfg.max_landmarks || n_obs > e->p.cfg.max_obs) fits[si] = 0;      // (the host path reports it, as it always did)
-        s.frame_flags.assign(std::max<size_t>(s.good.size(), 1), 0);
-        flags[si] = s.frame_flags.data();
+        idle[si] = !s.staged;
+        fits[si] = prepare_frame(e, s, fr[si]);
+        flags[si] = idle[si] ? nullptr : s.frame_flags.data();
         return (int)ISV_OK;
     });
-    if (rc != ISV_OK) { e->err = errs[0]; return rc; }
-    const auto tr1 = std::chrono::steady_clock::now();
-    bool fit_all = true;
-    for (int si = 0; si < S; si++) fit_all &= fits[si] != 0;
-    if (!e->dbg_unsupported_fired && e->resident_frames == e->dbg_unsupported_frame) { fit_all = false; e->dbg_unsupported_fired = true; }      // (test hook, once)
-    // isv_backend_seq_frame refuses a frame BEFORE it launches anything (capacity, or windows the per-window kernels do not take):
-    // the device still holds the state of the previous solve
-    rc = fit_all ? isv_backend_seq_frame(e->backend, S, fr.data(), res.data(), flags.data(), nullptr) : (int)ISV_ERR_UNSUPPORTED;
-    if (rc == ISV_ERR_CAPACITY || rc == ISV_ERR_UNSUPPORTED) {
-        const int rcl = leave_resident(e, true, true);
-        if (rcl != ISV_OK) return rcl;
+    const auto tr1 = clk::now();
+    // the hand-over (a frame is refused BEFORE anything is launched: the device still holds the previous solve's state)
+    rc = frame_fits(e, fits) ? isv_backend_seq_frame(e->backend, S, fr.data(), res.data(), flags.data(), nullptr) : (int)ISV_ERR_UNSUPPORTED;
+    if (rc == ISV_ERR_CAPACITY || rc == ISV_ERR_UNSUPPORTED) {      // the fall-back
+        rc = leave_resident(e, true, true);
+        if (rc != ISV_OK) return rc;
         e->resident_fallbacks++;
-        return RESIDENT_FELL_BACK;                   // isv_estimator_step goes on with the host path for this frame (the features are in)
+        fell_back = true;
+        return ISV_OK;
     }
     if (rc != ISV_OK) { e->err = std::string("resident frame failed: ") + isv_backend_last_error(e->backend); return rc; }
     for (Sequence &s : e->seq) s.features_added = false;
-    int n_active = 0;
-    for (int si = 0; si < S; si++) n_active += !idle[si];
-    const auto tr2 = std::chrono::steady_clock::now();
+    const int n_active = S - (int)std::count(idle.begin(), idle.end(), 1);
+    const auto tr2 = clk::now();
     e->resident_frames++;
     bool failed = false;
     for (int si = 0; si < S; si++) failed |= !idle[si] && res[si].summary.status != ISV_OK;
-    if (failed) {
-        // a non-finite solve: everything comes back to the host (the device has not slid the sequences of this frame yet; an idle one's
-        // slide of its last solve is still pending and is applied first) and the host path's policy applies
-        rc = leave_resident(e, false, false, &idle);
-        if (rc != ISV_OK) return rc;
-        for (int si = 0; si < S; si++) {          // the sequences that did solve still install their marginalisation outputs
-            Sequence &s = e->seq[si];
-            isv_marg_result_t m;
-            if (idle[si] || res[si].summary.status != ISV_OK || !s.margin_old) continue;
-            rc = isv_backend_seq_marg(e->backend, si, &m);
-            if (rc != ISV_OK) { e->err = isv_backend_last_error(e->backend); return rc; }
-            if (!m.valid) continue;
-            s.add_pose_prior = m.forward_pose_prior; s.add_relpose = m.backward_relpose; s.add_vb = m.backward_vb; s.have_to_add = true;
-            isv_rollpitch_t brp = m.backward_rollpitch; brp.index = s.Nvo - 1;
-            s.rollpitch.push_back(brp);
-        }
-    }
+    if (failed) { rc = recover_failed_frame(e, idle, res); if (rc != ISV_OK) return rc; }
     (void)parallel_for(S, errs, [&](int si, std::string &) {
-        Sequence &s = e->seq[si];
-        if (idle[si]) return (int)ISV_OK;          // (nothing was solved for it: no slide, no row, its counters stand)
-        const int N = s.N;
-        const isv_seq_result_t &r = res[si];
-        const bool ok = r.summary.status == ISV_OK;
-        if (!failed) {      // the frames the host reads: newest (processIMU), oldest and second (pose_output.txt rows)
-            std::memcpy(s.Ps[N - 1].data(), r.Ps_new, 24); std::memcpy(s.Rs[N - 1].data(), r.Rs_new, 72); std::memcpy(s.Vs[N - 1].data(), r.Vs_new, 24);
-            std::memcpy(s.Bas[N - 1].data(), r.Bas_new, 24); std::memcpy(s.Bgs[N - 1].data(), r.Bgs_new, 24);
-            std::memcpy(s.Ps[0].data(), r.Ps_old, 24); std::memcpy(s.Rs[0].data(), r.Rs_old, 72);
-            std::memcpy(s.Ps[1].data(), r.Ps_second, 24); std::memcpy(s.Rs[1].data(), r.Rs_second, 72);
-            for (size_t l = 0; l < s.good.size(); l++) s.tracks[s.good[l]].solve_flag = s.frame_flags[l];
-            if (e->p.cfg.estimate_extrinsic) { std::memcpy(s.cur_tic, r.tic, 24); std::memcpy(s.cur_ric, r.ric, 72); s.have_ex = true; }
-        } else if (!ok) { s.n_failed++; s.have_to_add = false; }
-        s.last_summary = r.summary;
-        s.n_solves++;
-        s.n_good_last = (int)s.good.size();
-        after_solve(e, s, s.Headers[N - 1]);
-        s.last_slide = s.margin_old ? 1 : 2;
-        if (failed && !ok) { s.flag = INITIAL_STRUCTURE; s.rollpitch.clear(); }
+        if (!idle[si]) finish_resident(e, e->seq[si], res[si], failed);      // (idle: nothing was solved for it -- no slide, no row, its counters stand)
         return (int)ISV_OK;
     });
-    auto msd = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    e->step_ms[1] = msd(tr0, tr1); e->step_ms[4] = msd(tr1, tr2); e->step_ms[5] = msd(tr2, std::chrono::steady_clock::now());
+    e->step_ms[1] = ms(tr0, tr1); e->step_ms[4] = ms(tr1, tr2); e->step_ms[5] = ms(tr2, clk::now());
     return n_active;
 }
 
@@ -907,61 +926,40 @@ extern "C" int isv_estimator_set_resident(isv_estimator_t *e, int32_t on) {
 extern "C" int64_t isv_estimator_resident_frames(const isv_estimator_t *e) { return e ? e->resident_frames : 0; }
 extern "C" int64_t isv_estimator_resident_fallbacks(const isv_estimator_t *e) { return e ? e->resident_fallbacks : -1; }
 
-// Estimator::processImage (src/estimator.cpp:126-215) on every staged sequence, the solves batched
-extern "C" int isv_estimator_step(isv_estimator_t *e) {
-    if (!e) return ISV_ERR_INVALID_ARG;
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = clk::now();
-    for (double &x : e->step_ms) x = 0;
-    std::vector<std::string> errs;
-    if (e->resident_ready) {
-        // (round 4: a sequence WITHOUT an image this step no longer evicts the group -- it idles on the device, src/System.cpp:160-202
-        //  pairs IMU and images per sequence -- but every sequence must be resident and in steady state)
-        bool all = true, any = false;
-        for (const Sequence &s : e->seq) { all &= s.resident && s.flag == NON_LINEAR; any |= s.staged; }
-        if (!any) return 0;
-        // the resident store's own limits, checked BEFORE anything is mutated.  First the cheap upper bound (every staged id taken as a
-        // new track); a sequence that fails it is counted exactly -- only the ids it does not track yet open a track (a tight
-        // handle that really fits used to fail the bound on every frame and fall back to the slower path without a word)
-        bool fits = true;
-        for (const Sequence &s : e->seq) {
-            if (!s.staged) continue;
-            auto ok = [&](size_t n_new) {
-                const size_t fresh = n_new > s.free_slots.size() ? n_new - s.free_slots.size() : 0;
-                return s.tracks.size() + n_new <= (size_t)e->tracks_cap && s.pool.size() / POINT_RING + fresh <= (size_t)e->tracks_cap;
-            };
-            if (ok(s.staged_image.size())) continue;
-            std::vector<int> ids(s.tracks.size());
-            for (size_t i = 0; i < s.tracks.size(); i++) ids[i] = s.tracks[i].id;
-            std::sort(ids.begin(), ids.end());
-            size_t n_new = 0;
-            for (const auto &ob : s.staged_image) n_new += !std::binary_search(ids.begin(), ids.end(), ob.first);
-            fits &= ok(n_new);
-        }
-        if (!e->dbg_precheck_fired && e->resident_frames == e->dbg_precheck_frame) { fits = false; e->dbg_precheck_fired = true; }      // (test hook, once)
-        if (all && fits) {
-            const int rc = resident_frame(e, errs);        // (fills step_ms[1] host preparation, [4] hand-over + device, [5] read-back + slide)
-            e->step_ms[0] = ms(t0, clk::now());
-            if (rc != RESIDENT_FELL_BACK) return rc;
-            // the frame did not fit the resident path: the windows are back, this frame's features are already in the track lists
-        } else {
-            e->resident_fallbacks++;
-            const int rc = leave_resident(e, true);    // a sequence left the steady state, or the store is full:
-            if (rc != ISV_OK) return rc;               // the host path takes over (and seeds again once every sequence solves in one frame)
-        }
+namespace {
+
+// The phases of isv_estimator_step.  The resident gate: every sequence is resident and steady, and the staged images fit the track
+// store (by the cheap bound, every id a new track, else counted exactly).  Refuses nothing; mutates only its once-only test hook.
+bool resident_gate(isv_estimator *e) {
+    bool all = true, fits = true;
+    for (const Sequence &s : e->seq) {
+        all &= s.resident && s.flag == NON_LINEAR;
+        if (!s.staged) continue;
+        auto ok = [&](size_t n_new) {
+            const size_t fresh = n_new > s.free_slots.size() ? n_new - s.free_slots.size() : 0;
+            return s.tracks.size() + n_new <= (size_t)e->tracks_cap && s.pool.size() / POINT_RING + fresh <= (size_t)e->tracks_cap;
+        };
+        if (ok(s.staged_image.size())) continue;
+        std::vector<int> ids(s.tracks.size());
+        for (size_t i = 0; i < s.tracks.size(); i++) ids[i] = s.tracks[i].id;
+        std::sort(ids.begin(), ids.end());
+        size_t n_new = 0;
+        for (const auto &ob : s.staged_image) n_new += !std::binary_search(ids.begin(), ids.end(), ob.first);
+        fits &= ok(n_new);
     }
-    // per sequence: addFeatureAndCheckParallax, Headers, the INITIAL bookkeeping; mark[si] = 1 when the sequence solves
+    if (!e->dbg_precheck_fired && e->resident_frames == e->dbg_precheck_frame) { fits = false; e->dbg_precheck_fired = true; }
+    return all && fits;
+}
+
+// The feature pass: image, INITIAL bookkeeping and window of each sequence that solves (-> solve).  Refuses a full INITIAL window
+// without a bootstrap, and what build_window refuses; mutates the sequences.
+int feature_pass(isv_estimator *e, std::vector<std::string> &errs, std::vector<int> &solve) {
     std::vector<char> mark(e->seq.size(), 0);
-    int rc = parallel_for((int)e->seq.size(), errs, [&](int si, std::string &err) {
+    const int rc = parallel_for((int)e->seq.size(), errs, [&](int si, std::string &err) {
         Sequence &s = e->seq[si];
         if (!s.staged && !s.features_added) return (int)ISV_OK;
         if (s.flag == INITIAL && s.frame_count == s.N - 1 && !s.have_boot) { err = "the window is full: isv_estimator_set_bootstrap first"; return (int)ISV_ERR_INVALID_ARG; }
-        if (!s.features_added) {                   // (else: the resident path ran addFeatureAndCheckParallax for this image before it fell back)
-            s.margin_old = add_features(s, e->p.min_parallax);
-            s.Headers[s.frame_count] = s.staged_header;
-            s.staged = false;
-        }
+        if (!s.features_added) take_image(e, s, false);      // (else: the resident path took this image before it fell back)
         s.features_added = false;
         if (s.flag == INITIAL) {
             if (s.frame_count == s.N - 1) {
@@ -973,19 +971,20 @@ extern "C" int isv_estimator_step(isv_estimator_t *e) {
         return mark[si] ? build_window(e, s, err) : (int)ISV_OK;
     });
     if (rc != ISV_OK) { e->err = errs[0]; return rc; }
-    std::vector<int> solve;
     for (size_t si = 0; si < e->seq.size(); si++) if (mark[si]) solve.push_back((int)si);
-    if (solve.empty()) return 0;
-    // solveOdometry (:461-472): f_manager.triangulate(Ps, tic, ric); backendOptimization()
+    return ISV_OK;
+}
+
+// The solve, solveOdometry (:461-472).  Refuses what the solver refuses; mutates the windows, the depths and the first-time solvers.
+int solve_windows(isv_estimator *e, const std::vector<int> &solve, std::vector<isv_summary_t> &sums, std::vector<isv_marg_result_t> &margs, SolveStamps &st) {
     std::vector<isv_window_t *> ws(solve.size());
     for (size_t k = 0; k < solve.size(); k++) ws[k] = &e->seq[solve[k]].w;
-    bool first_solve = false;
-    for (int si : solve) first_solve |= e->seq[si].flag == INITIAL_STRUCTURE;
-    std::vector<isv_summary_t> sums(solve.size());
-    std::vector<isv_marg_result_t> margs(solve.size());
-    const auto t1 = clk::now();
-    auto t2 = t1, t3 = t1;
-    if (!first_solve && e->solver.solve_odometry_batch) {
+    std::vector<int> first;
+    for (int si : solve) if (e->seq[si].flag == INITIAL_STRUCTURE) first.push_back(si);
+    sums.resize(solve.size()); margs.resize(solve.size());
+    st.set_up = st.triangulated = st.initialised = clk::now();
+    int rc;
+    if (first.empty() && e->solver.solve_odometry_batch) {       // steady state: one hand-over
         rc = e->solver.solve_odometry_batch(e->solver.ctx, (int32_t)ws.size(), ws.data(), sums.data(), margs.data());
         if (rc != ISV_OK) { e->err = "solveOdometry failed"; return rc; }
     } else {
@@ -995,11 +994,9 @@ extern "C" int isv_estimator_step(isv_estimator_t *e) {
             Sequence &s = e->seq[si];
             for (size_t l = 0; l < s.good.size(); l++) s.tracks[s.good[l]].depth = s.wdepth[l];
         }
-        t2 = clk::now();
+        st.triangulated = clk::now();
         // backendOptimization(), INITIAL_STRUCTURE branch (:1543-1548): vector2double, initFactorGraph, NON_LINEAR.  The
         // NON_LINEAR branch below runs in the same call (two `if`s in the reference, not else-if).
-        std::vector<int> first;
-        for (int si : solve) if (e->seq[si].flag == INITIAL_STRUCTURE) first.push_back(si);
         if (!first.empty() && e->solver.init_factor_graph_batch) {       // all first solves of this frame in one batch
             std::vector<isv_window_t *> wf(first.size());
             for (size_t k = 0; k < first.size(); k++) wf[k] = &e->seq[first[k]].w;
@@ -1008,8 +1005,7 @@ extern "C" int isv_estimator_step(isv_estimator_t *e) {
             if (rc != ISV_OK) { e->err = "initFactorGraph failed"; return rc; }
         } else {
             for (int si : first) {
-                isv_summary_t s0;
-                double kld = 0;
+                isv_summary_t s0; double kld = 0;
                 rc = e->solver.init_factor_graph(e->solver.ctx, &e->seq[si].w, &s0, &kld);
                 if (rc != ISV_OK) { e->err = "initFactorGraph failed"; return rc; }
             }
@@ -1023,46 +1019,66 @@ extern "C" int isv_estimator_step(isv_estimator_t *e) {
             rc = build_window(e, s, e->err);
             if (rc != ISV_OK) return rc;
         }
-        t3 = clk::now();
+        st.initialised = clk::now();
         rc = e->solver.optimize_batch(e->solver.ctx, (int32_t)ws.size(), ws.data(), sums.data(), margs.data());
         if (rc != ISV_OK) { e->err = "backendOptimization failed"; return rc; }
     }
-    const auto t4 = clk::now();
-    (void)parallel_for((int)solve.size(), errs, [&](int k, std::string &) {
-        Sequence &s = e->seq[solve[k]];
-        // A solve that produced a non-finite cost must not be copied into the window (the reference has no such guard:
-        // its NaNs would spread through every later frame): the sequence keeps its pre-solve states and depths, drops
-        // this frame's marginalisation outputs, and the failure is counted (isv_estimator_failed_solves).  The window
-        // still slides (below), but without marginalisation outputs the prior factors cannot follow it -- with MARGIN_OLD
-        // they would sit one frame off for every later solve -- so the sequence goes back to INITIAL_STRUCTURE after the
-        // slide: its next solve rebuilds EVERY prior at the then-current states through initFactorGraph
-        // (backendOptimization's first branch, src/estimator.cpp:1543-1548), exactly as after initialisation.
-        const bool ok = sums[k].status == ISV_OK;
-        if (ok) read_back(s); else { s.n_failed++; s.have_to_add = false; }
-        const isv_marg_result_t &m = margs[k];
-        if (ok && s.margin_old && m.valid) {
-            s.add_pose_prior = m.forward_pose_prior; s.add_relpose = m.backward_relpose; s.add_vb = m.backward_vb;
-            s.have_to_add = true;
-            isv_rollpitch_t brp = m.backward_rollpitch;
-            brp.index = s.Nvo - 1;
-            s.rollpitch.push_back(brp);                 // vioRollPitchEdges.push_back  (MargBackward :1536-1538)
+    st.solved = clk::now();
+    return ISV_OK;
+}
+
+// Post-solve of one sequence: a finite solve is read back and its marginalisation outputs installed.  Mutates only it.
+void post_solve(const isv_estimator *e, Sequence &s, const isv_summary_t &summary, const isv_marg_result_t &m) {
+    const bool ok = summary.status == ISV_OK;
+    if (ok) { read_back(s); if (s.margin_old) install_marg(s, m); }
+    finish_solve(e, s, summary, ok);
+}
+
+// The seeding decision: every sequence solved this frame and is steady.  Refuses a failed seed, but not CAPACITY / UNSUPPORTED.
+int seed_if_steady(isv_estimator *e, size_t n_solved) {
+    if (!e->resident_mode || e->resident_ready || n_solved != e->seq.size()) return ISV_OK;
+    for (const Sequence &s : e->seq) if (!(s.flag == NON_LINEAR && s.frame_count == s.N - 1 && !s.have_to_add)) return ISV_OK;
+    const int rc = seed_resident(e);
+    return rc == ISV_ERR_CAPACITY || rc == ISV_ERR_UNSUPPORTED ? (int)ISV_OK : rc;
+}
+
+}  // namespace
+
+// Estimator::processImage (src/estimator.cpp:126-215) on every staged sequence, the solves batched
+extern "C" int isv_estimator_step(isv_estimator_t *e) {
+    if (!e) return ISV_ERR_INVALID_ARG;
+    const auto t0 = clk::now();
+    for (double &x : e->step_ms) x = 0;
+    std::vector<std::string> errs;
+    if (e->resident_ready) {
+        bool any = false;
+        for (const Sequence &s : e->seq) any |= s.staged;
+        if (!any) return 0;
+        if (resident_gate(e)) {
+            bool fell_back = false;
+            const int rc = resident_frame(e, errs, fell_back);
+            e->step_ms[0] = ms(t0, clk::now());
+            if (!fell_back) return rc;
+        } else {
+            e->resident_fallbacks++;
+            const int rc = leave_resident(e, true);    // a sequence left the steady state, or the store is full:
+            if (rc != ISV_OK) return rc;               // the host path takes over (and seeds again once every sequence solves in one frame)
         }
-        s.last_summary = sums[k];
-        s.n_solves++;
-        s.n_good_last = (int)s.good.size();
-        after_solve(e, s, s.Headers[s.N - 1]);        // (slides as NON_LINEAR: removeBackShiftDepth re-hosts the depths)
-        if (!ok) { s.flag = INITIAL_STRUCTURE; s.rollpitch.clear(); }
-        return (int)ISV_OK;
-    });
-    if (e->resident_mode && !e->resident_ready && solve.size() == e->seq.size()) {
-        // every sequence solved this frame and is in steady state: from the next frame on the windows stay on the device
-        bool all = true;
-        for (const Sequence &s : e->seq) all &= s.flag == NON_LINEAR && s.frame_count == s.N - 1 && !s.have_to_add;
-        if (all) { const int rcs = seed_resident(e); if (rcs != ISV_OK && rcs != ISV_ERR_CAPACITY && rcs != ISV_ERR_UNSUPPORTED) return rcs; }
     }
-    const auto t5 = clk::now();
-    e->step_ms[0] = ms(t0, t5); e->step_ms[1] = ms(t0, t1); e->step_ms[2] = ms(t1, t2); e->step_ms[3] = ms(t2, t3);
-    e->step_ms[4] = ms(t3, t4); e->step_ms[5] = ms(t4, t5);
+    std::vector<int> solve;
+    int rc = feature_pass(e, errs, solve);
+    if (rc != ISV_OK || solve.empty()) return rc;
+    std::vector<isv_summary_t> sums;
+    std::vector<isv_marg_result_t> margs;
+    SolveStamps st;
+    rc = solve_windows(e, solve, sums, margs, st);
+    if (rc != ISV_OK) return rc;
+    (void)parallel_for((int)solve.size(), errs, [&](int k, std::string &) { post_solve(e, e->seq[solve[k]], sums[k], margs[k]); return (int)ISV_OK; });
+    rc = seed_if_steady(e, solve.size());
+    if (rc != ISV_OK) return rc;
+    const clk::time_point t[6] = {t0, st.set_up, st.triangulated, st.initialised, st.solved, clk::now()};      // step_ms[k] = t[k - 1] .. t[k]
+    e->step_ms[0] = ms(t[0], t[5]);
+    for (int k = 1; k <= 5; k++) e->step_ms[k] = ms(t[k - 1], t[k]);
     return (int)solve.size();
 }
 
