@@ -4,8 +4,9 @@
  *   CombinedFactors::operator+            include/factor/pose_graph_factors.h:27-51   (edge composition, host)
  *   PoseGraph::optimizeCS (one pass)      src/pose_graph/pose_graph.cpp:234-428       (MI355X)
  *   loop_pose_output.txt                  src/pose_graph/pose_graph.cpp:412-423       (host)
- * Loop DETECTION (DBoW query, BRIEF matching, PnP-RANSAC: keyframe.cpp, pose_graph.cpp:123-223) stays in the reference:
- * its result arrives here as the keyframe's has_loop / loop_index / loop_info / loop_weight members.
+ * The geometric VERIFICATION of a loop candidate (BRIEF matching, PnP-RANSAC: keyframe.cpp:231-295) is isvins_loop.h; its
+ * result arrives here as the keyframe's has_loop / loop_index / loop_info / loop_weight members (isv_loop_apply).  The DBoW
+ * query that proposes the candidate (pose_graph.cpp:123-223) stays in the reference.
  *
  * What optimizeCS solves (Ceres 2.0.0, external): poses of the keyframes first_looped_index .. cur_index, 7-parameter
  * blocks with PoseLocalParameterization; the first one (and every keyframe of sequence 0) constant; residual blocks, in

@@ -22,9 +22,15 @@ enum { ISV_INIT_ALIGN, ISV_INIT_SFM, ISV_INIT_RELPOSE, ISV_INIT_STAGES };
 // a stage's state on the handle: its device block (grow-only, freed with the handle), its kernel events, its last call's times
 struct InitSlot {
     void *d = nullptr; size_t cap = 0;
-    hipEvent_t ev[2] = {};
-    double call_ms = 0, kernel_ms = 0;
+    hipEvent_t ev[3] = {};        // before the kernels, after them, between two of them
+    double call_ms = 0, kernel_ms = 0, part_ms[2] = {};   // part_ms: each kernel of a two-kernel stage
 };
+// the slot's end: its block and events (the owning handle's device is selected)
+inline void init_slot_free(InitSlot &s) {
+    if (s.d) (void)hipFree(s.d);
+    for (auto &e : s.ev) if (e) (void)hipEventDestroy(e);
+    s = InitSlot{};
+}
 
 // a block of buffers, laid out section by section: each starts 256-byte aligned (the kernels read every section by pointer)
 struct BlockLayout {

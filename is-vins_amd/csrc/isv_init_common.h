@@ -1,11 +1,13 @@
 /*
- * isv_init_common.h -- serial pieces shared by the initialisation kernels (isv_sfm.hip, isv_relpose.hip) and by the CPU
- * restatement of the relative-pose stage (tests/native/isv_relpose_oracle.c).  Plain C that compiles as HIP device code
+ * isv_init_common.h -- serial pieces shared by the initialisation kernels (isv_sfm.hip, isv_relpose.hip), the loop-closure
+ * kernel (isv_loop.hip) and the CPU restatements of the relative-pose stage and of the loop verification
+ * (tests/native/isv_relpose_oracle.c, tests/native/isv_loop_oracle.c).  Plain C that compiles as HIP device code
  * (ISV_HD) or as host C.  Every includer turns FP contraction off for its whole translation unit (#pragma clang fp
  * contract(off) in the kernels, gcc -ffp-contract=off for the restatement): the operations below then round the same way on
  * both sides, and only the device and host libm (sqrt is exact; acos / cos / pow / log) can round apart.
  *
  *   svd_jacobi            Eigen 3.3 JacobiSVD of a square matrix (two-sided 2 x 2 Jacobi sweeps, no QR preconditioner)
+ *   eig_jacobi_sym        cyclic Jacobi eigen-decomposition of a symmetric matrix (EPnP's M^T M, the DLT's L^T L: isv_loop_common.h)
  *   isv_excitation_var    Estimator::checkIMUExcitation's var (src/estimator.cpp:213-238), the first stage of both kernels
  *   rp_*                  the relative-pose RANSAC (isv_relpose.h): OpenCV 3.2's cv::RNG, RANSACPointSetRegistrator's
  *                         getSubset and RANSACUpdateNumIters, fundam.cpp's run7Point / computeError, cv::solveCubic,
@@ -113,6 +115,54 @@ ISV_HD void svd_jacobi(int n, double *A, double *w, double *U, double *V) {
 }
 
 
+/* ---------------- symmetric eigen-decomposition, cyclic Jacobi (n <= 12) ---------------- */
+/* A row-major symmetric, overwritten; w: eigenvalues, descending (first on ties); V: n x n row-major, COLUMN k the eigenvector
+ * of w[k].  A rotation is skipped when |A_pq| <= 2 eps max|A_ii| (the largest diagonal seen so far, as svd_jacobi does), so a
+ * null space comes out as whatever orthonormal basis the sweeps leave. */
+ISV_HD void eig_jacobi_sym(int n, double *A, double *w, double *V) {
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) V[i * n + j] = i == j ? 1.0 : 0.0;
+    double maxDiag = 0;
+    for (int i = 0; i < n; i++) maxDiag = fabs(A[i * n + i]) > maxDiag ? fabs(A[i * n + i]) : maxDiag;
+    int finished = 0;
+    for (int sweep = 0; !finished && sweep < 64; sweep++) {
+        finished = 1;
+        for (int p = 0; p < n - 1; p++)
+            for (int q = p + 1; q < n; q++) {
+                const double apq = A[p * n + q];
+                const double thr = 2.0 * DBL_EPSILON * maxDiag > DBL_MIN ? 2.0 * DBL_EPSILON * maxDiag : DBL_MIN;
+                if (!(fabs(apq) > thr)) continue;
+                finished = 0;
+                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+                const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+                for (int k = 0; k < n; k++) {   /* A <- A J */
+                    const double x = A[k * n + p], y = A[k * n + q];
+                    A[k * n + p] = c * x - s * y; A[k * n + q] = s * x + c * y;
+                }
+                for (int k = 0; k < n; k++) {   /* A <- J^T A */
+                    const double x = A[p * n + k], y = A[q * n + k];
+                    A[p * n + k] = c * x - s * y; A[q * n + k] = s * x + c * y;
+                }
+                for (int k = 0; k < n; k++) {   /* V <- V J */
+                    const double x = V[k * n + p], y = V[k * n + q];
+                    V[k * n + p] = c * x - s * y; V[k * n + q] = s * x + c * y;
+                }
+                const double ap = fabs(A[p * n + p]), aq = fabs(A[q * n + q]), mx = ap > aq ? ap : aq;
+                maxDiag = maxDiag > mx ? maxDiag : mx;
+            }
+    }
+    for (int i = 0; i < n; i++) w[i] = A[i * n + i];
+    for (int i = 0; i < n; i++) {
+        int pos = i;
+        for (int k = i + 1; k < n; k++) if (w[k] > w[pos]) pos = k;
+        if (pos != i) {
+            const double tw = w[i]; w[i] = w[pos]; w[pos] = tw;
+            for (int k = 0; k < n; k++) { const double tv = V[k * n + i]; V[k * n + i] = V[k * n + pos]; V[k * n + pos] = tv; }
+        }
+    }
+}
+
 /* checkIMUExcitation: the spread of delta_v / sum_dt over all_image_frame's entries 1 .. nf-1 (dv [nf][3], sdt [nf]) */
 ISV_HD double isv_excitation_var(int nf, const double *dv, const double *sdt) {
     double sum_g[3] = {0, 0, 0};   /* S1: never initialised in the reference; zero here */
@@ -141,11 +191,11 @@ ISV_HD uint32_t rp_uniform(uint64_t *state, uint32_t n) {
     return (uint32_t)s % n;
 }
 
-/* RANSACPointSetRegistrator::getSubset for 7 points: distinct indices, a repeated draw is drawn again.  3.2's
- * FMEstimatorCallback does not override checkSubset (no collinearity test) and checkPartialSubsets is false, so one subset
- * is exactly its draws. */
-ISV_HD void rp_subset(uint64_t *state, int count, int *idx) {
-    for (int i = 0; i < 7; i++)
+/* RANSACPointSetRegistrator::getSubset for m points: distinct indices, a repeated draw is drawn again.  Neither 3.2's
+ * FMEstimatorCallback (m = 7) nor its PnPRansacCallback (m = 5) overrides checkSubset (no collinearity test) and
+ * checkPartialSubsets is false, so one subset is exactly its draws. */
+ISV_HD void rp_subset_m(uint64_t *state, int count, int m, int *idx) {
+    for (int i = 0; i < m; i++)
         for (;;) {
             const int v = (int)rp_uniform(state, (uint32_t)count);
             int j = 0;
@@ -153,6 +203,7 @@ ISV_HD void rp_subset(uint64_t *state, int count, int *idx) {
             if (j == i) { idx[i] = v; break; }
         }
 }
+ISV_HD void rp_subset(uint64_t *state, int count, int *idx) { rp_subset_m(state, count, 7, idx); }
 
 /* RANSACUpdateNumIters(p, ep, modelPoints, maxIters); cvRound is round-half-even (rint) */
 ISV_HD int rp_update_num_iters(double p, double ep, int model_points, int max_iters) {

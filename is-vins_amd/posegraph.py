@@ -143,6 +143,16 @@ def clone_keyframes(kf):
     return out
 
 
+def pose_graph_truth(n_keyframes):
+    """make_pose_graph's ground truth: positions [K,3] and rotations (list of K 3x3) on the closed figure-eight"""
+    K = n_keyframes
+    s = np.arange(K) / K * 2 * np.pi * 2                     # two laps: the second lap revisits the first
+    P = np.stack([4.0 * np.sin(s), 2.0 * np.sin(2 * s), 0.3 * np.sin(3 * s)], 1)
+    yaw = 0.8 * np.sin(s) + 0.3
+    Rt = [synth._rot_zyx(yaw[k], 0.1 * np.sin(2 * s[k]), 0.08 * np.cos(s[k])) for k in range(K)]
+    return P, Rt
+
+
 def make_pose_graph(seed, n_keyframes=120, n_loops=3, drift=0.002, loop_noise=0.005, sequence=1, rollpitch_every=1):
     """A keyframe list as PoseGraphBuilder / PoseGraph::addKeyFrame leave it: truth on a closed figure-eight (so that
     places are revisited), VIO poses = the truth composed with an accumulating drift, keyfactor->relativePoseFactor =
@@ -151,10 +161,8 @@ def make_pose_graph(seed, n_keyframes=120, n_loops=3, drift=0.002, loop_noise=0.
     comes from the truth + loop_noise.  Returns (ctypes keyframe array, truth positions [K,3], first_looped_index)."""
     rng = synth.SplitMix64(0x9E0_0000_0000 + int(seed))
     K = n_keyframes
-    s = np.arange(K) / K * 2 * np.pi * 2                     # two laps: the second lap revisits the first
-    P = np.stack([4.0 * np.sin(s), 2.0 * np.sin(2 * s), 0.3 * np.sin(3 * s)], 1)
-    yaw = 0.8 * np.sin(s) + 0.3
-    Rt = [synth._rot_zyx(yaw[k], 0.1 * np.sin(2 * s[k]), 0.08 * np.cos(s[k])) for k in range(K)]
+    s = np.arange(K) / K * 2 * np.pi * 2
+    P, Rt = pose_graph_truth(K)
     # drift: a slowly turning similarity-free error, integrated along the chain (4-dof dominant: yaw + translation)
     e = rng.normal(6 * K).reshape(K, 6)
     vioP, vioR = [P[0].copy()], [Rt[0].copy()]
