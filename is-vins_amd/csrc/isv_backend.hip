@@ -68,6 +68,7 @@ static int create_impl(isv_backend *h) {
     d.force_invalid = getenv("ISV_DEBUG_FORCE_INVALID") ? atoi(getenv("ISV_DEBUG_FORCE_INVALID")) : 0;
     d.min_radius = getenv("ISV_DEBUG_MIN_RADIUS") ? atof(getenv("ISV_DEBUG_MIN_RADIUS")) : 1e-32;
     if (!(d.min_radius > 0)) d.min_radius = 1e-32;
+    if (const char *e = getenv("ISV_DEBUG_SFM_BA_ITERS")) { const int k = atoi(e); if (k >= 0 && k <= 50) h->sfm_ba_iters = k; }
     d.prior_strip_sz = PR_REL0 + PR_REL_SZ * (c.n_vo - 1) + PR_RP_SZ * c.max_rollpitch;
     memcpy(d.proj_sqrt_info, c.proj_sqrt_info, sizeof(d.proj_sqrt_info));
     memcpy(d.G, c.gravity, sizeof(d.G));

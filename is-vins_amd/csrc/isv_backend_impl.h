@@ -80,6 +80,7 @@ struct isv_backend {
     int device = 0;               // the HIP device the handle was created on; every entry point re-selects it
     double *init_scratch = nullptr, *init_kld = nullptr;   // initFactorGraph scratch, allocated on first use and kept
     size_t init_cap = 0;
+    int sfm_ba_iters = 50;        // max_num_iterations of the SfM stage's BA (test hook, env ISV_DEBUG_SFM_BA_ITERS = 0..50, read at creation)
     InitSlot init_slot[ISV_INIT_STAGES];   // the batched initialisation stages' blocks, events and times (isv_init_launch.h)
     double last_ms[8] = {};
     int64_t last_counts[8] = {};

@@ -468,7 +468,7 @@ __device__ double ba_model(const BA &B) {
 }
 
 // TrustRegionMinimizer + LevenbergMarquardtStrategy (the restatement's ba_solve); every lane keeps the same scalar state
-__device__ void ba_solve(const BA &B, isv_sfm_result_t *out) {
+__device__ void ba_solve(const BA &B, isv_sfm_result_t *out, int max_it) {
     const int t = threadIdx.x, nc = B.nc;
     double radius = 1e4, decrease_factor = 2.0;
     int reuse = 0, invalid = 0, it = 0, term = ISV_TERM_RUNNING, nsucc = 0;
@@ -484,7 +484,7 @@ __device__ void ba_solve(const BA &B, isv_sfm_result_t *out) {
     double x_norm = sqrt(ba_norm2(B, B.cq, B.ct, B.X, 3, nullptr, nullptr, nullptr, 0));
     if (t == 0) out->ba_initial_cost = x_cost;
     for (;;) {
-        if (it >= 50) { term = ISV_TERM_MAX_ITERATIONS; break; }
+        if (it >= max_it) { term = ISV_TERM_MAX_ITERATIONS; break; }   // 50, or the handle's ISV_DEBUG_SFM_BA_ITERS
         if (gmax <= 1e-10) { term = ISV_TERM_GRADIENT_TOL; break; }
         if (radius <= 1e-32) { term = ISV_TERM_MIN_RADIUS; break; }
         it++;
@@ -556,7 +556,7 @@ __global__ void __launch_bounds__(kLanes) k_sfm(const SfmHdr *__restrict__ hdrs,
                                                 const int32_t *__restrict__ pt_off_g, const int32_t *__restrict__ pt_trk_g, const double *__restrict__ pt_uv_g,
                                                 const double *__restrict__ dv_g, const double *__restrict__ sdt_g, double *__restrict__ scratch,
                                                 isv_sfm_result_t *__restrict__ results, double *__restrict__ pos_out, int32_t *__restrict__ st_out,
-                                                int nt_max, int no_max, int nS) {
+                                                int nt_max, int no_max, int nS, int ba_max_it) {
     const SfmHdr &H = hdrs[blockIdx.x];
     isv_sfm_result_t *res = results + blockIdx.x;
     const int t = threadIdx.x;
@@ -693,7 +693,7 @@ __global__ void __launch_bounds__(kLanes) k_sfm(const SfmHdr *__restrict__ hdrs,
     B.nact = (int)misc[M_N]; B.nw = nw; B.l = l; B.nc = 6 * nw - 9;
     B.cq = cq; B.ct = ct; B.cqc = cqc; B.ctc = ctc; B.csc = csc; B.cD = cD; B.cdiag = cdiag; B.cg = cg; B.cdx = cdx; B.cdel = cdel;
     B.rhs = rhs; B.S = S; B.misc = misc;
-    ba_solve(B, res);
+    ba_solve(B, res, ba_max_it);
     for (int j = t; j < ntr; j += kLanes) {
         st_out[H.trk_off + j] = st[j];
         for (int k = 0; k < 3; k++) pos_out[3 * ((size_t)H.trk_off + j) + k] = st[j] ? X[3 * j + k] : 0.0;
@@ -880,7 +880,7 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
             hipLaunchKernelGGL(k_sfm, dim3(n), dim3(kLanes), lds, h->stream, (const SfmHdr *)(d + o_hd), (const isv_sfm_track_t *)(d + o_tr),
                                (const double *)(d + o_obs), (const int32_t *)(d + o_poff), (const int32_t *)(d + o_ptrk), (const double *)(d + o_uv),
                                (const double *)(d + o_dv), (const double *)(d + o_sdt), (double *)(d + o_scr), (isv_sfm_result_t *)(d + o_res),
-                               (double *)(d + o_pos), (int32_t *)(d + o_st), nt_max, no_max, nS);
+                               (double *)(d + o_pos), (int32_t *)(d + o_st), nt_max, no_max, nS, h->sfm_ba_iters);
         },
         {{results, o_res, sizeof(isv_sfm_result_t) * n}, {pos.data(), o_pos, 24 * n_tr}, {st.data(), o_st, 4 * n_tr}},
         [&] {

@@ -137,6 +137,16 @@ void isvo_lp_epnp(int n, const double *X, const double *uv, double *R, double *t
 }
 void isvo_eig_jacobi_sym(int n, double *A, double *w, double *V) { eig_jacobi_sym(n, A, w, V); }
 void isvo_rodrigues_v2m(const double *rv, double *R) { rodrigues_v2m(rv, R, NULL); }
+void isvo_rodrigues_v2m_J(const double *rv, double *R, double *J) { rodrigues_v2m(rv, R, J); }   /* J: 3 x 9, d R / d r_i */
+void isvo_rodrigues_m2v(const double *R, double *rv) { rodrigues_m2v(R, rv); }
+/* cvProjectPoints2 of one point from rvec / tvec: err [2] and J [2 x 6] */
+void isvo_pnp_project(const double *rvec, const double *tvec, const double *X, const double *m, double *err, double *J) {
+    double R[9], dRdr[27];
+    rodrigues_v2m(rvec, R, dRdr);
+    pnp_project(R, dRdr, tvec, X, m, err, J);
+}
+/* CvLevMarq::step: JtJ 6 x 6 (its lower triangle is read), JtE [6] */
+void isvo_pnp_step(const double *JtJ, const double *JtE, int lambdaLg10, const double *prev, double *param) { pnp_step(JtJ, JtE, lambdaLg10, prev, param); }
 double isvo_lp_point_error(const double *rvec, const double *tvec, const float *X, const float *uv) {
     double R[9];
     lp_match_t m;

@@ -26,6 +26,9 @@
 static int g_quirk_off = 0;
 void isvo_sfm_set_quirks_off(int mask) { g_quirk_off = mask; }
 #define FR(x) ((g_quirk_off & 2) ? (x) : (double)(float)(x))
+/* test hook: the BA's max_num_iterations (the library's ISV_DEBUG_SFM_BA_ITERS); outside 0..50 means the default, 50 */
+static int g_ba_max_it = 50;
+void isvo_sfm_set_ba_max_iterations(int k) { g_ba_max_it = (k >= 0 && k <= 50) ? k : 50; }
 
 /* ---------------- Eigen 3.3 JacobiSVD, square n x n (n <= 6), no QR preconditioner ---------------- */
 /* A row-major, overwritten; w: singular values (sorted, descending); U (may be NULL), V: n x n row-major */
@@ -642,7 +645,7 @@ static void ba_solve(const ba_t *B, double *cq, double *ct, double *X, isv_sfm_r
     double x_norm = sqrt(ba_norm2(B, cq, ct, X, NULL, NULL, NULL));
     out->ba_initial_cost = x_cost;
     for (;;) {
-        if (it >= 50) { term = ISV_TERM_MAX_ITERATIONS; break; }
+        if (it >= g_ba_max_it) { term = ISV_TERM_MAX_ITERATIONS; break; }
         if (gmax <= 1e-10) { term = ISV_TERM_GRADIENT_TOL; break; }
         if (radius <= 1e-32) { term = ISV_TERM_MIN_RADIUS; break; }
         it++;
@@ -903,6 +906,11 @@ int isvo_sfm(const isv_sfm_problem_t *p, isv_sfm_result_t *res) {
         res->is_key_frame[f] = 0;
     }
     return res->status = ISV_SFM_OK;
+}
+
+/* unit entry: one observation's residual and its unscaled 2 x 3 Jacobians (quaternion tangent, translation, point); q w x y z */
+void isvo_sfm_ba_obs(const double *q, const double *t, const double *X, const double *uv, double *r, double *Jq, double *Jt, double *JX) {
+    ba_obs(q, t, X, uv, r, Jq, Jt, JX);
 }
 
 int isvo_sfm_sizeof(int which) {
