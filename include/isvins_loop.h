@@ -7,7 +7,7 @@
  * for many (current keyframe, old keyframe) pairs in one call.  Its result is what isvins_posegraph.h consumes: the
  * has_loop / loop_index / loop_info / loop_weight members of isv_pg_keyframe_t (isv_loop_apply writes them).
  *
- * Not here: the DBoW query that proposes old_index (PoseGraph::detectLoop; its vocabulary is not part of this project),
+ * Not here: the DBoW query that proposes old_index (PoseGraph::detectLoop: include/isvins_bow.h, whose loop_index it is),
  * BRIEF extraction and FAST (they need images), addKeyFrame's sequence shift and earliest_loop_index bookkeeping
  * (pose_graph.cpp:59-110).  The candidate and the descriptors are inputs.  point_2d_uv and point_id are only compacted by
  * findConnection and never read, so the pair does not carry them; point_2d_norm is carried (the reference's KeyFrame has
