@@ -8,7 +8,7 @@
  * has_loop / loop_index / loop_info / loop_weight members of isv_pg_keyframe_t (isv_loop_apply writes them).
  *
  * Not here: the DBoW query that proposes old_index (PoseGraph::detectLoop: include/isvins_bow.h, whose loop_index it is),
- * BRIEF extraction and FAST (they need images), addKeyFrame's sequence shift and earliest_loop_index bookkeeping
+ * BRIEF extraction and FAST (include/isvins_keyframe.h), addKeyFrame's sequence shift and earliest_loop_index bookkeeping
  * (pose_graph.cpp:59-110).  The candidate and the descriptors are inputs.  point_2d_uv and point_id are only compacted by
  * findConnection and never read, so the pair does not carry them; point_2d_norm is carried (the reference's KeyFrame has
  * it) and, like them, never read.

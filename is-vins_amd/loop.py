@@ -4,7 +4,7 @@ distance gate and loop_weight) for many keyframe pairs in one call.  `LoopVerifi
 missing or there is no GPU: no CPU path.
 
 `make_loop_scene` builds deterministic synthetic pairs for the tests and scripts/loop_bench.py; descriptors and the loop
-candidate are inputs (BRIEF extraction and the DBoW query are not part of this package)."""
+candidate are inputs (the DBoW query is bow.py, the extraction of descriptors and corners from an image keyframe.py)."""
 import ctypes as C
 
 import numpy as np
