@@ -22,6 +22,7 @@
 #include <vector>
 #include "isv_init_launch.h"
 #include "isv_keyframe.h"
+#include "isv_pinhole.h"
 
 namespace {
 
@@ -37,18 +38,13 @@ struct KfHdr {                    // host-packed per-item record
     uint64_t img_off;             // into the packed images (and the blurred images, and the score maps)
 };
 
-struct KfCam {                    // PinholeCamera's members, formed once at creation
-    double inv_K11, inv_K13, inv_K22, inv_K23, k1, k2, p1, p2;
-    int32_t no_distortion, pad;
-};
-
 struct KfLast { int32_t status, W, H; uint64_t img_off; };
 
 }  // namespace
 
 struct isv_kf {
     isv_kf_config_t cfg;
-    KfCam cam;
+    PinholeCam cam;
     std::string err;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -249,17 +245,10 @@ __global__ void __launch_bounds__(kSelThreads) k_kf_select(const KfHdr *__restri
 // (int) of a float32, toward zero (K1); a value outside int's range is outside every image
 __device__ __forceinline__ int kf_trunc(float f) { return (f > -2147483648.0f && f < 2147483648.0f) ? (int)f : -1; }
 
-__device__ __forceinline__ void kf_distortion(const KfCam &c, double x, double y, double *dx, double *dy) {
-    const double mx2_u = x * x, my2_u = y * y, mxy_u = x * y, rho2_u = mx2_u + my2_u;
-    const double rad_dist_u = c.k1 * rho2_u + c.k2 * rho2_u * rho2_u;
-    *dx = x * rad_dist_u + 2.0 * c.p1 * mxy_u + c.p2 * (rho2_u + 2.0 * mx2_u);
-    *dy = y * rad_dist_u + 2.0 * c.p2 * mxy_u + c.p1 * (rho2_u + 2.0 * my2_u);
-}
-
 __global__ void __launch_bounds__(kBriefWaves * kLanes) k_kf_brief(const KfHdr *__restrict__ hdrs, const isv_kf_result_t *__restrict__ results,
                                                                     const uint8_t *__restrict__ blur, const int8_t *__restrict__ pattern,
                                                                     const float *__restrict__ pts, const uint32_t *__restrict__ kp_xy,
-                                                                    const uint8_t *__restrict__ kp_sc, const KfCam cam, uint64_t *__restrict__ brief,
+                                                                    const uint8_t *__restrict__ kp_sc, const PinholeCam cam, uint64_t *__restrict__ brief,
                                                                     float *__restrict__ uv, float *__restrict__ norm, uint8_t *__restrict__ score,
                                                                     uint64_t *__restrict__ wbrief) {
     __shared__ int8_t pat[4][256];
@@ -310,19 +299,7 @@ __global__ void __launch_bounds__(kBriefWaves * kLanes) k_kf_brief(const KfHdr *
             const size_t o = k_off + j;
             uv[2 * o] = px; uv[2 * o + 1] = py;
             score[o] = kp_sc[H.slot_off + j];
-            // PinholeCamera::liftProjective
-            const double mx_d = cam.inv_K11 * (double)px + cam.inv_K13, my_d = cam.inv_K22 * (double)py + cam.inv_K23;
-            double mx_u = mx_d, my_u = my_d;
-            if (!cam.no_distortion) {
-                double dx, dy;
-                kf_distortion(cam, mx_d, my_d, &dx, &dy);
-                mx_u = mx_d - dx; my_u = my_d - dy;
-                for (int it = 1; it < 8; it++) {
-                    kf_distortion(cam, mx_u, my_u, &dx, &dy);
-                    mx_u = mx_d - dx; my_u = my_d - dy;
-                }
-            }
-            norm[2 * o] = (float)(mx_u / 1.0); norm[2 * o + 1] = (float)(my_u / 1.0);
+            pinhole_lift(cam, px, py, &norm[2 * o], &norm[2 * o + 1]);       // PinholeCamera::liftProjective (isv_pinhole.h)
         }
     }
 }
@@ -367,9 +344,7 @@ extern "C" int isv_kf_create(const isv_kf_config_t *c, isv_kf_t **out) {
     if (!(c->fx > 0) || !(c->fy > 0)) return ISV_ERR_INVALID_ARG;
     isv_kf *h = new isv_kf();
     h->cfg = *c;
-    // PinholeCamera::PinholeCamera / setParameters: m_inv_K11 = 1.0 / fx, m_inv_K13 = -cx / fx, m_inv_K22, m_inv_K23, m_noDistortion
-    h->cam = KfCam{1.0 / c->fx, -c->cx / c->fx, 1.0 / c->fy, -c->cy / c->fy, c->k1, c->k2, c->p1, c->p2,
-                   (c->k1 == 0.0 && c->k2 == 0.0 && c->p1 == 0.0 && c->p2 == 0.0) ? 1 : 0, 0};
+    h->cam = pinhole_make(c->fx, c->fy, c->cx, c->cy, c->k1, c->k2, c->p1, c->p2);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e == hipSuccess && ndev <= 0) e = hipErrorNoDevice;
