@@ -1,6 +1,6 @@
 // isv_marg.hip -- k_marg: Estimator::MargForward (reference src/estimator.cpp:1149-1352) and
-// Estimator::MargBackward (:1354-1539) on the device, one wavefront per window (only windows
-// uploaded with margin_old != 0 do work).  All matrices are tiny (<= 30x30) and live in LDS; the
+// Estimator::MargBackward (:1354-1539) on the device, one workgroup of one or four wavefronts per
+// window (only windows uploaded with margin_old != 0 do work).  All matrices are tiny (<= 30x30) and live in LDS; the
 // wavefront cooperates lane-per-entry.  Runs after k_finalize: it linearises at the para_* arrays
 // (d.pose / d.sb / d.lam, the un-rotated solve output) with the post-update, post-double2vector
 // priors, and takes Ri/ti from the rotated Rs[0]/Ps[0] -- exactly the reference's order of events
@@ -24,6 +24,17 @@
 #define MSTAMP(k) do {} while (0)
 #endif
 #define SYNC() __syncthreads()
+// The barrier of the cooperative helpers below.  WV = false: the workgroup's (the helpers' TS lanes are the whole workgroup).
+// WV = true: the helper runs on ONE wavefront of a wider workgroup, beside other wavefronts doing other work (k_marg_bwd<3>): its
+// lanes run in lockstep and the LDS serves a wavefront's accesses in order, so all it needs is that the compiler keeps the
+// accesses on their side of this point and that the writes have left the wavefront (workgroup-scope fences, no s_barrier).
+template <bool WV> DEV void tsync() {
+    if constexpr (WV) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else __syncthreads();
+}
 
 // The arithmetic of one Jacobi rotation, written with explicit fma() so that every instance (the one-wavefront loops, the
 // four-wavefront kernel) rounds the same way whatever the compiler would have contracted: their results are bitwise equal.
@@ -49,56 +60,61 @@ DEV void jr_block(double ca, double sa, double cb, double sb, double b00, double
 DEV void jr_vec(double c, double sn, double vp, double vq, double &op, double &oq) { op = fma(c, vp, -(sn * vq)); oq = fma(sn, vp, c * vq); }
 
 // ---- wave-cooperative dense helpers on LDS matrices (row-major) --------------------------------
+template <int TS = MT, bool WV = false>
 DEV void w_mm(const double *A, const double *B, double *C, int m, int k, int n, int t) {
-    for (int e = t; e < m * n; e += MT) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[i * k + p] * B[p * n + j]; C[e] = s; }
-    SYNC();
+    for (int e = t; e < m * n; e += TS) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[i * k + p] * B[p * n + j]; C[e] = s; }
+    tsync<WV>();
 }
+template <int TS = MT, bool WV = false>
 DEV void w_mm_tn(const double *A, const double *B, double *C, int m, int k, int n, int t) {    // A is k x m
-    for (int e = t; e < m * n; e += MT) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[p * m + i] * B[p * n + j]; C[e] = s; }
-    SYNC();
+    for (int e = t; e < m * n; e += TS) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[p * m + i] * B[p * n + j]; C[e] = s; }
+    tsync<WV>();
 }
+template <int TS = MT, bool WV = false>
 DEV void w_mm_nt(const double *A, const double *B, double *C, int m, int k, int n, int t) {    // B is n x k
-    for (int e = t; e < m * n; e += MT) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[i * k + p] * B[j * k + p]; C[e] = s; }
-    SYNC();
+    for (int e = t; e < m * n; e += TS) { const int i = e / n, j = e % n; double s = 0; for (int p = 0; p < k; p++) s += A[i * k + p] * B[j * k + p]; C[e] = s; }
+    tsync<WV>();
 }
 // inverse by Gauss-Jordan with partial pivoting on the augmented [A | I]; W is n x 2n scratch
+template <int TS = MT, bool WV = false>
 DEV void w_inv(const double *A, int n, double *Inv, double *W, int *piv, int t) {
     const int n2 = 2 * n;
-    for (int e = t; e < n * n2; e += MT) { const int i = e / n2, j = e % n2; W[e] = (j < n) ? A[i * n + j] : ((j - n) == i ? 1.0 : 0.0); }
-    SYNC();
+    for (int e = t; e < n * n2; e += TS) { const int i = e / n2, j = e % n2; W[e] = (j < n) ? A[i * n + j] : ((j - n) == i ? 1.0 : 0.0); }
+    tsync<WV>();
     for (int k = 0; k < n; k++) {
         if (t == 0) { int p = k; double best = fabs(W[k * n2 + k]); for (int i = k + 1; i < n; i++) if (fabs(W[i * n2 + k]) > best) { best = fabs(W[i * n2 + k]); p = i; } piv[0] = p; }
-        SYNC();
+        tsync<WV>();
         const int p = piv[0];
-        if (p != k) for (int j = t; j < n2; j += MT) { const double tmp = W[k * n2 + j]; W[k * n2 + j] = W[p * n2 + j]; W[p * n2 + j] = tmp; }
-        SYNC();
+        if (p != k) for (int j = t; j < n2; j += TS) { const double tmp = W[k * n2 + j]; W[k * n2 + j] = W[p * n2 + j]; W[p * n2 + j] = tmp; }
+        tsync<WV>();
         const double d = W[k * n2 + k];
-        SYNC();
-        for (int j = t; j < n2; j += MT) W[k * n2 + j] /= d;
-        SYNC();
-        for (int e = t; e < n * n2; e += MT) {
+        tsync<WV>();
+        for (int j = t; j < n2; j += TS) W[k * n2 + j] /= d;
+        tsync<WV>();
+        for (int e = t; e < n * n2; e += TS) {
             const int i = e / n2, j = e % n2;
             if (i != k && j != k) W[e] -= W[i * n2 + k] * W[k * n2 + j];
         }
-        SYNC();
-        for (int i = t; i < n; i += MT) if (i != k) W[i * n2 + k] = 0.0;
-        SYNC();
+        tsync<WV>();
+        for (int i = t; i < n; i += TS) if (i != k) W[i * n2 + k] = 0.0;
+        tsync<WV>();
     }
-    for (int e = t; e < n * n; e += MT) { const int i = e / n, j = e % n; Inv[e] = W[i * n2 + n + j]; }
-    SYNC();
+    for (int e = t; e < n * n; e += TS) { const int i = e / n, j = e % n; Inv[e] = W[i * n2 + n + j]; }
+    tsync<WV>();
 }
 // U = LLT(M).matrixL().transpose()  (upper triangular), lane-parallel over rows
+template <int TS = MT, bool WV = false>
 DEV void w_chol_upper(const double *M, int n, double *U, double *L, int t) {
-    for (int e = t; e < n * n; e += MT) L[e] = M[e];
-    SYNC();
+    for (int e = t; e < n * n; e += TS) L[e] = M[e];
+    tsync<WV>();
     for (int j = 0; j < n; j++) {
         if (t == 0) { double dd = L[j * n + j]; for (int k = 0; k < j; k++) dd -= L[j * n + k] * L[j * n + k]; L[j * n + j] = sqrt(dd); }
-        SYNC();
-        for (int i = j + 1 + t; i < n; i += MT) { double s = L[i * n + j]; for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k]; L[i * n + j] = s / L[j * n + j]; }
-        SYNC();
+        tsync<WV>();
+        for (int i = j + 1 + t; i < n; i += TS) { double s = L[i * n + j]; for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k]; L[i * n + j] = s / L[j * n + j]; }
+        tsync<WV>();
     }
-    for (int e = t; e < n * n; e += MT) { const int i = e / n, j = e % n; U[e] = (j >= i) ? L[j * n + i] : 0.0; }
-    SYNC();
+    for (int e = t; e < n * n; e += TS) { const int i = e / n, j = e % n; U[e] = (j >= i) ? L[j * n + i] : 0.0; }
+    tsync<WV>();
 }
 // Jacobi eigen-decomposition with a round-robin (tournament) ordering: the floor(n/2) rotations of a
 // round touch disjoint index pairs, so they are computed and applied together (3 barriers per round
@@ -263,29 +279,31 @@ DEV void w_jacobi(double *A, int n, double *wv, double *V, double *tmp, int t) {
     else w_jacobi_t<0>(A, n, wv, V, tmp, t);
 }
 // log(det(A)) of a symmetric positive-definite matrix by unpivoted elimination (lane-parallel)
+template <int TS = MT, bool WV = false>
 DEV double w_logdet_spd(const double *A, int n, double *W, int t) {
-    for (int e = t; e < n * n; e += MT) W[e] = A[e];
-    SYNC();
+    for (int e = t; e < n * n; e += TS) W[e] = A[e];
+    tsync<WV>();
     double ld = 0;
     for (int k = 0; k < n; k++) {
         const double d = W[k * n + k];
         ld += log(d);
-        SYNC();
-        for (int e = t; e < n * n; e += MT) { const int i = e / n, j = e % n; if (i > k && j > k) W[e] -= W[i * n + k] * W[k * n + j] / d; }
-        SYNC();
+        tsync<WV>();
+        for (int e = t; e < n * n; e += TS) { const int i = e / n, j = e % n; if (i > k && j > k) W[e] -= W[i * n + k] * W[k * n + j] / d; }
+        tsync<WV>();
     }
     return ld;
 }
 // Sigma = (Jk U) D^-1 (Jk U)^T over the kept eigenpairs (keep[i] != 0); Jk is rows x n
+template <int TS = MT, bool WV = false>
 DEV void w_project_cov(const double *Jk, int rows, int n, const double *V, const double *wv, const int *keep, double *JU, double *Sigma, int t) {
-    for (int e = t; e < rows * n; e += MT) { const int a = e / n, k = e % n; double s = 0; for (int c = 0; c < n; c++) s += Jk[a * n + c] * V[c * n + k]; JU[e] = s; }
-    SYNC();
-    for (int e = t; e < rows * rows; e += MT) {
+    for (int e = t; e < rows * n; e += TS) { const int a = e / n, k = e % n; double s = 0; for (int c = 0; c < n; c++) s += Jk[a * n + c] * V[c * n + k]; JU[e] = s; }
+    tsync<WV>();
+    for (int e = t; e < rows * rows; e += TS) {
         const int a = e / rows, b = e % rows; double s = 0;
         for (int k = 0; k < n; k++) if (keep[k]) s += JU[a * n + k] * (1.0 / wv[k]) * JU[b * n + k];
         Sigma[e] = s;
     }
-    SYNC();
+    tsync<WV>();
 }
 DEV double w_det(const double *A, int n, double *W, int *piv, int t) {     // via LU with partial pivoting (single lane; n <= 21)
     double det = 1;
@@ -579,19 +597,15 @@ template __global__ void k_marg_fwd<256>(DevBatch);
 //     parameter table), the other wavefronts wait at the barrier: two barriers per round, ~210 instructions per window.
 // Rotations, their order and the arithmetic of each item (jr_params / jr_block / jr_vec) are those of w_jacobi_pipe: the
 // result is bitwise the same.  In: Lp at ws[0..n^2).  Out: V at ws[896..), eigenvalues at ws[1344..).
+// The body, for a workgroup of 256 lanes: sA (n x n, written by the caller, no barrier needed before the call) is destroyed, its
+// diagonal ends as the eigenvalues; sV receives the eigenvectors.  Returns behind a barrier.  (k_marg_jacobi and k_marg_bwd<3>)
 template <int NC>
-__global__ __launch_bounds__(256) void k_marg_jacobi(DevBatch d) {
+DEV void jacobi4(double *sA, double *sV, int t) {
     constexpr int n = NC, m = n + (n & 1), half = m / 2, NI = half * half, NN = n * n;
     static_assert(NI <= 128 && half <= 32, "one item per lane of two wavefronts");
-    __shared__ double sA[NN + 1], sV[NN + 1], red[8], sink[2], rc[2][32], rs[2][32];
+    __shared__ double red[8], sink[2], rc[2][32], rs[2][32];
     __shared__ int rp[2][32], rq[2][32];
-    const int w = blockIdx.x, t = threadIdx.x;
-    if (!d.margin_old[w] || ISV_SEQ_IDLE(d, w)) return;
-#ifdef ISV_STAMP
-    unsigned long long t_last = wall_clock64();
-#endif
-    double *const ws = d.marg_ws + (size_t)w * ISV_MARG_WS;
-    for (int e = t; e < NN; e += 256) { sA[e] = ws[e]; sV[e] = (e / n == e % n) ? 1.0 : 0.0; }
+    for (int e = t; e < NN; e += 256) sV[e] = (e / n == e % n) ? 1.0 : 0.0;
     __syncthreads();
     const bool is_block = t < 128;                    // wavefront-uniform
     const int e = is_block ? t : t - 128;
@@ -651,6 +665,19 @@ __global__ __launch_bounds__(256) void k_marg_jacobi(DevBatch d) {
             if (r + 1 < m - 1) { params(r + 1, buf ^ 1); __syncthreads(); }
         }
     }
+}
+template <int NC>
+__global__ __launch_bounds__(256) void k_marg_jacobi(DevBatch d) {
+    constexpr int n = NC, NN = n * n;
+    __shared__ double sA[NN + 1], sV[NN + 1];
+    const int w = blockIdx.x, t = threadIdx.x;
+    if (!d.margin_old[w] || ISV_SEQ_IDLE(d, w)) return;
+#ifdef ISV_STAMP
+    unsigned long long t_last = wall_clock64();
+#endif
+    double *const ws = d.marg_ws + (size_t)w * ISV_MARG_WS;
+    for (int e = t; e < NN; e += 256) sA[e] = ws[e];
+    jacobi4<NC>(sA, sV, t);
     for (int x = t; x < NN; x += 256) ws[896 + x] = sV[x];
     if (t < n) ws[1344 + t] = sA[t * n + t];
 #ifdef ISV_STAMP
@@ -659,11 +686,126 @@ __global__ __launch_bounds__(256) void k_marg_jacobi(DevBatch d) {
 }
 template __global__ void k_marg_jacobi<21>(DevBatch);
 
+// ---- the serial pieces of MargBackward's build phase, as routines: the one-wavefront kernels run them on lane 0 one after
+// another, k_marg_bwd<3> gives each its own wavefront ------------------------------------------------------------------
+// raw (unweighted) Jacobian 15 x 30 of IMU factor f into M1 (zeroed by the caller).  `pieces` selects which of its independent
+// 3 x 3 blocks this call forms and stores (every block by the expressions below, whoever calls): the calls of one window
+// together cover IRJ_ALL, and no entry of M1 belongs to two pieces.  (The blocks that are mere copies: imu_raw_copies.)
+enum { IRJ_RIT = 1, IRJ_S = 2, IRJ_B1 = 4, IRJ_T = 8, IRJ_B2 = 16, IRJ_ALL = 31 };
+DEV void imu_raw_jac(const DevBatch &d, size_t f, const double *pi, const double *si, double *M1, int pieces) {
+    const double *rec = d.imu_in + f * ISV_IMU_IN;
+    const double *pj = pi + 7, *sj = si + 9;
+    Quat Qi = q_from_pose(pi), Qj = q_from_pose(pj), Qii = q_inv(Qi);
+    const double dt = rec[IMU_DT];
+    double dbg[3], tt[3], u[3], o1[3], o2[3], RiT[9], S1[9], S2[9], B1[9], B2[9], L[9], Rr[9], T[9];
+    Quat dq = Quat{rec[IMU_DQ + 3], rec[IMU_DQ], rec[IMU_DQ + 1], rec[IMU_DQ + 2]};
+    Quat cdq = dq;
+    if (pieces & (IRJ_B1 | IRJ_B2)) {
+        for (int k = 0; k < 3; k++) dbg[k] = si[6 + k] - rec[IMU_LBG + k];
+        m3v(rec + IMU_DQ_DBG, dbg, tt);
+        cdq = q_mul(dq, q_delta(tt));
+    }
+    if (pieces & IRJ_RIT) q_to_R(Qii, RiT);
+    if (pieces & IRJ_S) {
+        for (int k = 0; k < 3; k++) u[k] = 0.5 * d.G[k] * dt * dt + pj[k] - pi[k] - si[k] * dt;
+        q_rot(Qii, u, o1);
+        for (int k = 0; k < 3; k++) u[k] = d.G[k] * dt + sj[k] - si[k];
+        q_rot(Qii, u, o2);
+        skew3(o1, S1); skew3(o2, S2);
+    }
+    if (pieces & IRJ_B1) {
+        Quat aq = q_mul(q_inv(Qj), Qi);
+        qleft33(aq, L); qright33(cdq, Rr); m3_mul(L, Rr, B1);
+        const double av[3] = {aq.x, aq.y, aq.z}, bv[3] = {cdq.x, cdq.y, cdq.z};
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) B1[r * 3 + c] += av[r] * (-bv[c]);
+    }
+    if (pieces & IRJ_T) {
+        qleft33(q_mul(q_mul(q_inv(Qj), Qi), dq), L);
+        m3_mul(L, rec + IMU_DQ_DBG, T);
+    }
+    if (pieces & IRJ_B2) qleft33(q_mul(q_mul(q_inv(cdq), Qii), Qj), B2);
+    for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) {
+        const int ab = a * 3 + b;
+        if (pieces & IRJ_RIT) {
+            M1[(0 + a) * 30 + 0 + b] = -RiT[ab]; M1[(0 + a) * 30 + 6 + b] = -RiT[ab] * dt; M1[(6 + a) * 30 + 6 + b] = -RiT[ab];
+            M1[(0 + a) * 30 + 15 + b] = RiT[ab]; M1[(6 + a) * 30 + 21 + b] = RiT[ab];
+        }
+        if (pieces & IRJ_S) { M1[(0 + a) * 30 + 3 + b] = S1[ab]; M1[(6 + a) * 30 + 3 + b] = S2[ab]; }
+        if (pieces & IRJ_B1) M1[(3 + a) * 30 + 3 + b] = -B1[ab];
+        if (pieces & IRJ_T) M1[(3 + a) * 30 + 12 + b] = -T[ab];
+        if (pieces & IRJ_B2) M1[(3 + a) * 30 + 18 + b] = B2[ab];
+    }
+}
+// entry ab of the Jacobian's blocks that are copies: the preintegration's bias Jacobians and the identities
+DEV void imu_raw_copies(const DevBatch &d, size_t f, double *M1, int ab) {
+    const double *rec = d.imu_in + f * ISV_IMU_IN;
+    const int a = ab / 3, b = ab % 3;
+    M1[(0 + a) * 30 + 9 + b] = -rec[IMU_DP_DBA + ab]; M1[(0 + a) * 30 + 12 + b] = -rec[IMU_DP_DBG + ab];
+    M1[(6 + a) * 30 + 9 + b] = -rec[IMU_DV_DBA + ab]; M1[(6 + a) * 30 + 12 + b] = -rec[IMU_DV_DBG + ab];
+    M1[(9 + a) * 30 + 9 + b] = (a == b) ? -1.0 : 0.0; M1[(12 + a) * 30 + 12 + b] = (a == b) ? -1.0 : 0.0;
+    M1[(9 + a) * 30 + 24 + b] = (a == b) ? 1.0 : 0.0; M1[(12 + a) * 30 + 27 + b] = (a == b) ? 1.0 : 0.0;
+}
+// the VB prior on sb[v-1] (J = I, info = S^T S) into Lam's VB0 block (lanes t, t + stride, ...)
+DEV void lin9_info(const double *S, double *Lam, int t, int stride) {
+    for (int e = t; e < 81; e += stride) { const int a = e / 9, b = e % 9; double s = 0; for (int k = 0; k < 9; k++) s += S[k * 9 + a] * S[k * 9 + b]; Lam[(21 + a) * 30 + 21 + b] += s; }
+}
+// the recovered factors' measurements at the current estimate (into the record) and the non-trivial blocks of their Jacobian:
+// the relative pose's d/d pose_{v-1} in sJ[0..36) and d/d pose_v in sJ[36..72), the roll-pitch factor's 2 x 3 in BmBy[0..6),
+// the yaw factor's 1 x 3 in BmBy[6..9).  Depends on the poses only.
+DEV void recovered_jac(const double *pose, const double *sb, int v, isv_relpose_t &rp, isv_linear9_t &vb, isv_rollpitch_t &gp, double *sJ, double *BmBy) {
+    const double *PSi = pose + 7 * (v - 1), *PSj = pose + 7 * v;
+    Quat Qi = q_from_pose(PSi), Qj = q_from_pose(PSj);
+    double dd[3] = {PSj[0] - PSi[0], PSj[1] - PSi[1], PSj[2] - PSi[2]};
+    q_rot(q_inv(Qi), dd, rp.delta_t); q_to_R(q_mul(q_inv(Qi), Qj), rp.delta_R);
+    rp.imu_i = v - 1; rp.imu_j = v;
+    double r6[6];
+    relpose_jac(rp.delta_t, rp.delta_R, PSi, PSj, r6, sJ, sJ + 36);
+    for (int k = 0; k < 9; k++) vb.VB[k] = sb[9 * v + k];
+    vb.index = v;
+    q_to_R(Qi, gp.R); gp.index = v - 1;
+    // RollPitchFactor(Qw)::EvaluateOnlyJacobians, YawFactor(Qw)::EvaluateOnlyJacobians at pose v-1
+    Quat Ri = q_normalized(Qi), Rm = q_from_R(gp.R);
+    double nZ[3] = {0, 0, -1.0}, vv[3], S[9], Rmm[9], Bm[9];
+    q_rot(so3_mul(Rm, q_conj(Ri)), nZ, vv);
+    skew3(vv, S); q_to_R(Rm, Rmm); m3_mul(S, Rmm, Bm);
+    double exv[3] = {1, 0, 0}, ym[3], Rr[9], Sy[9], By[9];
+    q_rot(q_inv(Qi), exv, ym);
+    q_to_R(Ri, Rr); skew3(ym, Sy);
+    for (int k = 0; k < 9; k++) Rr[k] = -Rr[k];
+    m3_mul(Rr, Sy, By);
+    for (int k = 0; k < 6; k++) BmBy[k] = Bm[k];
+    for (int k = 0; k < 3; k++) BmBy[6 + k] = By[3 + k];
+}
+// entry (a, b) of the recovered factors' 21 x 21 Jacobian from recovered_jac's blocks: 0 + the block's entry, as the sums into
+// the zeroed matrix gave it (the blocks do not overlap)
+DEV double recovered_jac_entry(int a, int b, const double *sJ, const double *BmBy) {
+    double x = 0.0;
+    if (a < 6) { if (b >= 15) x += sJ[a * 6 + b - 15]; else if (b < 6) x += sJ[36 + a * 6 + b]; }
+    else if (a < 15) { if (b == a) x += 1.0; }
+    else if (a < 17) { if (b >= 18) x += BmBy[(a - 15) * 3 + b - 18]; }
+    else if (a < 20) { if (b == a - 2) x += 1.0; }
+    else if (b >= 18) x += BmBy[6 + b - 18];
+    return x;
+}
+
 // MargBackward.  In three launches: <0> builds the 21 x 21 marginal Lp and the recovered factors' Jacobian Jr (left in
 // d.marg_ws), k_marg_jacobi<21> eigen-decomposes Lp, <1> projects the covariance onto the factors and takes the KLD.
 // In one launch: <2>, the eigen-decomposition by the window's one wavefront (w_jacobi_pipe).
+// <3>: one launch of FOUR wavefronts per window.  The one-wavefront forms are bound by the window's latency, and much of that
+// is serial: chains of quaternion / 3 x 3 products on lane 0, five projections whose pivot chains follow each other, entry
+// loops of 441-900 items through 64 lanes.  Here the entry loops run over 256 lanes, the independent lane-0 chains each on a
+// wavefront of their own, the eigen-decomposition is k_marg_jacobi's (jacobi4), and the five projections run three at a time
+// on wavefronts 0-2 with wavefront-level synchronisation and their own slices of the scratch.  Every entry is formed by the
+// arithmetic of the other forms: the records are bytewise theirs.
 template <int PART>
-__global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
+__global__ __launch_bounds__(PART == 3 ? 256 : MT, PART == 3 ? 6 : 1) void k_marg_bwd(DevBatch d) {
+    // (<3>: at most 80 registers, so that a SIMD holds a wavefront of each of four workgroups beside one of k_marg_fwd<64> (160
+    // registers): 4 x 80 + 160 <= 512.  It wants 108; the lane-0 chains spill 28, which costs less than a second resident round.
+    // With the Schur loop below unrolled it wanted 224 and spilled 150: the build phase took 70 us per window instead of 25.)
+    constexpr int NTH = PART == 3 ? 256 : MT;               // lanes of the entry loops
+    constexpr int SCHUR_UNROLL = PART == 3 ? 1 : 9;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    (void)lane; (void)wid;
     // LDS is what limits residency (one wavefront per window, all windows should be resident at once next to
     // k_marg_fwd's): Lam (30x30) is dead once the 21x21 marginal Lp exists, so the recovered-factor Jacobian Jr
     // and the projection scratch JU live in its space; M1 (Lp) is dead after the eigen-decomposition copy and
@@ -687,59 +829,36 @@ __global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
     if constexpr (PART != 1) {
     // ================= MargBackward =================
     // order: T1 = frame v (@0), VB1 (@6), T0 = frame v-1 (@15), VB0 (@21)
-    for (int e = t; e < 900; e += MT) Lam[e] = 0.0;
-    SYNC();
-    {
-        const double *S = d.lin9[w].sqrt_info;            // VB prior on sb[v-1]: J = I, info = S^T S
-        for (int e = t; e < 81; e += MT) { const int a = e / 9, b = e % 9; double s = 0; for (int k = 0; k < 9; k++) s += S[k * 9 + a] * S[k * 9 + b]; Lam[(21 + a) * 30 + 21 + b] += s; }
+    for (int e = t; e < 900; e += NTH) Lam[e] = 0.0;
+    if constexpr (PART != 3) {
+        SYNC();
+        lin9_info(d.lin9[w].sqrt_info, Lam, t, MT);       // VB prior on sb[v-1]: J = I, info = S^T S
         SYNC();
         // IMU factor v-1 -> v: weighted Jacobian = strip's J if the strips were taken at this point; they were not
         // (the last accepted point was never re-linearised), so rebuild: raw J through the linearise kernel's layout.
     }
     // raw (unweighted) IMU Jacobian 15x30 in M1 (columns: pose_i 0..5, sb_i 6..14, pose_j 15..20, sb_j 21..29)
-    for (int e = t; e < 450; e += MT) M1[e] = 0.0;
+    for (int e = t; e < 450; e += NTH) M1[e] = 0.0;
     SYNC();
-    if (t == 0) {
+    if constexpr (PART == 3) {
+        // four chains of quaternion and 3 x 3 products that do not depend on each other, a wavefront each (lane 0; lanes of ONE
+        // wavefront that take different chains would run them one after another), beside the Linear9 information block
         const size_t f = (size_t)w * (N - 1) + (v - 1);
-        const double *rec = d.imu_in + f * ISV_IMU_IN;
-        const double *pi = pose + 7 * (v - 1), *pj = pi + 7, *si = sb + 9 * (v - 1), *sj = si + 9;
-        Quat Qi = q_from_pose(pi), Qj = q_from_pose(pj), Qii = q_inv(Qi);
-        const double dt = rec[IMU_DT];
-        double dbg[3], tt[3], u[3], o1[3], o2[3], RiT[9], S1[9], S2[9], B1[9], B2[9], L[9], Rr[9], T[9];
-        for (int k = 0; k < 3; k++) dbg[k] = si[6 + k] - rec[IMU_LBG + k];
-        Quat dq = Quat{rec[IMU_DQ + 3], rec[IMU_DQ], rec[IMU_DQ + 1], rec[IMU_DQ + 2]};
-        m3v(rec + IMU_DQ_DBG, dbg, tt);
-        Quat cdq = q_mul(dq, q_delta(tt));
-        q_to_R(Qii, RiT);
-        for (int k = 0; k < 3; k++) u[k] = 0.5 * d.G[k] * dt * dt + pj[k] - pi[k] - si[k] * dt;
-        q_rot(Qii, u, o1);
-        for (int k = 0; k < 3; k++) u[k] = d.G[k] * dt + sj[k] - si[k];
-        q_rot(Qii, u, o2);
-        skew3(o1, S1); skew3(o2, S2);
-        Quat aq = q_mul(q_inv(Qj), Qi);
-        qleft33(aq, L); qright33(cdq, Rr); m3_mul(L, Rr, B1);
-        const double av[3] = {aq.x, aq.y, aq.z}, bv[3] = {cdq.x, cdq.y, cdq.z};
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) B1[r * 3 + c] += av[r] * (-bv[c]);
-        qleft33(q_mul(q_mul(q_inv(Qj), Qi), dq), L);
-        m3_mul(L, rec + IMU_DQ_DBG, T);
-        qleft33(q_mul(q_mul(q_inv(cdq), Qii), Qj), B2);
-        for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) {
-            const int ab = a * 3 + b;
-            M1[(0 + a) * 30 + 0 + b] = -RiT[ab]; M1[(0 + a) * 30 + 3 + b] = S1[ab]; M1[(3 + a) * 30 + 3 + b] = -B1[ab]; M1[(6 + a) * 30 + 3 + b] = S2[ab];
-            M1[(0 + a) * 30 + 6 + b] = -RiT[ab] * dt; M1[(0 + a) * 30 + 9 + b] = -rec[IMU_DP_DBA + ab]; M1[(0 + a) * 30 + 12 + b] = -rec[IMU_DP_DBG + ab];
-            M1[(3 + a) * 30 + 12 + b] = -T[ab]; M1[(6 + a) * 30 + 6 + b] = -RiT[ab]; M1[(6 + a) * 30 + 9 + b] = -rec[IMU_DV_DBA + ab];
-            M1[(6 + a) * 30 + 12 + b] = -rec[IMU_DV_DBG + ab];
-            M1[(9 + a) * 30 + 9 + b] = (a == b) ? -1.0 : 0.0; M1[(12 + a) * 30 + 12 + b] = (a == b) ? -1.0 : 0.0;
-            M1[(0 + a) * 30 + 15 + b] = RiT[ab]; M1[(3 + a) * 30 + 18 + b] = B2[ab]; M1[(6 + a) * 30 + 21 + b] = RiT[ab];
-            M1[(9 + a) * 30 + 24 + b] = (a == b) ? 1.0 : 0.0; M1[(12 + a) * 30 + 27 + b] = (a == b) ? 1.0 : 0.0;
-        }
+        if (wid == 0) { if (lane < 9) imu_raw_copies(d, f, M1, lane); if (lane == 0) imu_raw_jac(d, f, pose + 7 * (v - 1), sb + 9 * (v - 1), M1, IRJ_RIT | IRJ_S); }
+        else if (wid == 1) { if (lane == 0) recovered_jac(pose, sb, v, rp, vb, gp, sJ, wv); }
+        else if (wid == 2) { lin9_info(d.lin9[w].sqrt_info, Lam, lane, 64); if (lane == 0) imu_raw_jac(d, f, pose + 7 * (v - 1), sb + 9 * (v - 1), M1, IRJ_B1); }
+        else if (lane == 0) imu_raw_jac(d, f, pose + 7 * (v - 1), sb + 9 * (v - 1), M1, IRJ_T | IRJ_B2);
+    } else if (t == 0) {
+        const size_t f = (size_t)w * (N - 1) + (v - 1);
+        imu_raw_jac(d, f, pose + 7 * (v - 1), sb + 9 * (v - 1), M1, IRJ_ALL);
+        for (int ab = 0; ab < 9; ab++) imu_raw_copies(d, f, M1, ab);
     }
     SYNC();
     {   // SJ = sqrt_info (15x15) * J (15x30) -> M2; Lam += (SJ)^T (SJ) with the column permutation to [T1 VB1 T0 VB0]
         const double *S = d.imu_sqrt + ((size_t)w * (N - 1) + (v - 1)) * 225;
-        for (int e = t; e < 450; e += MT) { const int a = e / 30, c = e % 30; double s = 0; for (int k = 0; k < 15; k++) s += S[a * 15 + k] * M1[k * 30 + c]; M2[e] = s; }
+        for (int e = t; e < 450; e += NTH) { const int a = e / 30, c = e % 30; double s = 0; for (int k = 0; k < 15; k++) s += S[a * 15 + k] * M1[k * 30 + c]; M2[e] = s; }
         SYNC();
-        for (int e = t; e < 900; e += MT) {
+        for (int e = t; e < 900; e += NTH) {
             const int a = e / 30, b = e % 30;            // factor column order: [pose_i sb_i pose_j sb_j] -> Lam index: i-part at 15.., j-part at 0..
             const int ga = (a < 15) ? 15 + a : a - 15, gb = (b < 15) ? 15 + b : b - 15;
             double s = 0; for (int k = 0; k < 15; k++) s += M2[k * 30 + a] * M2[k * 30 + b];
@@ -750,49 +869,46 @@ __global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
     double *Lp = M1;                                     // 21 x 21
     {
         double *A99 = Wk, *Ainv = Wk + 100;
-        for (int e = t; e < 81; e += MT) A99[e] = Lam[(21 + e / 9) * 30 + 21 + e % 9];
+        for (int e = t; e < 81; e += NTH) A99[e] = Lam[(21 + e / 9) * 30 + 21 + e % 9];
         SYNC();
-        w_inv(A99, 9, Ainv, Wk + 200, piv, t);
-        for (int e = t; e < 441; e += MT) {
+        if constexpr (PART == 3) { if (wid == 0) w_inv<64, true>(A99, 9, Ainv, Wk + 200, piv, lane); SYNC(); }      // (a pivot chain: one wavefront, no workgroup barriers)
+        else w_inv(A99, 9, Ainv, Wk + 200, piv, t);
+        for (int e = t; e < 441; e += NTH) {
             const int a = e / 21, b = e % 21; double s = Lam[a * 30 + b];
+            // (<3>: rolled -- unrolled, the loop holds the 81 entries of Ainv in registers, 224 in all; same sums in the same order)
+#pragma unroll SCHUR_UNROLL
             for (int p = 0; p < 9; p++) { double tt = 0; for (int q = 0; q < 9; q++) tt += Ainv[p * 9 + q] * Lam[b * 30 + 21 + q]; s -= Lam[a * 30 + 21 + p] * tt; }
             Lp[e] = s;
         }
         SYNC();
     }
     // recovered factors at the current estimate
-    for (int e = t; e < 441; e += MT) Jr[e] = 0.0;
-    SYNC();
-    if (t == 0) {
-        const double *PSi = pose + 7 * (v - 1), *PSj = pose + 7 * v;
-        Quat Qi = q_from_pose(PSi), Qj = q_from_pose(PSj);
-        double dd[3] = {PSj[0] - PSi[0], PSj[1] - PSi[1], PSj[2] - PSi[2]};
-        q_rot(q_inv(Qi), dd, rp.delta_t); q_to_R(q_mul(q_inv(Qi), Qj), rp.delta_R);
-        rp.imu_i = v - 1; rp.imu_j = v;
-        double r6[6];
-        relpose_jac(rp.delta_t, rp.delta_R, PSi, PSj, r6, sJ, sJ + 36);
-        for (int k = 0; k < 9; k++) vb.VB[k] = sb[9 * v + k];
-        vb.index = v;
-        q_to_R(Qi, gp.R); gp.index = v - 1;
-        // RollPitchFactor(Qw)::EvaluateOnlyJacobians, YawFactor(Qw)::EvaluateOnlyJacobians at pose v-1
-        Quat Ri = q_normalized(Qi), Rm = q_from_R(gp.R);
-        double nZ[3] = {0, 0, -1.0}, vv[3], S[9], Rmm[9], Bm[9];
-        q_rot(so3_mul(Rm, q_conj(Ri)), nZ, vv);
-        skew3(vv, S); q_to_R(Rm, Rmm); m3_mul(S, Rmm, Bm);
-        double exv[3] = {1, 0, 0}, ym[3], Rr[9], Sy[9], By[9];
-        q_rot(q_inv(Qi), exv, ym);
-        q_to_R(Ri, Rr); skew3(ym, Sy);
-        for (int k = 0; k < 9; k++) Rr[k] = -Rr[k];
-        m3_mul(Rr, Sy, By);
-        for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) { Jr[a * 21 + 15 + b] += sJ[a * 6 + b]; Jr[a * 21 + b] += sJ[36 + a * 6 + b]; }
-        for (int a = 0; a < 9; a++) Jr[(6 + a) * 21 + 6 + a] += 1.0;
-        for (int a = 0; a < 2; a++) for (int b = 0; b < 3; b++) Jr[(15 + a) * 21 + 18 + b] += Bm[a * 3 + b];
-        for (int a = 0; a < 3; a++) Jr[(17 + a) * 21 + 15 + a] += 1.0;
-        for (int b = 0; b < 3; b++) Jr[20 * 21 + 18 + b] += By[3 + b];
+    if constexpr (PART == 3) {
+        // (their blocks were formed beside the IMU Jacobian: sJ, wv[0..9); an entry per lane)
+        for (int e = t; e < 441; e += NTH) Jr[e] = recovered_jac_entry(e / 21, e % 21, sJ, wv);
+    } else {
+        for (int e = t; e < 441; e += MT) Jr[e] = 0.0;
+        SYNC();
+        if (t == 0) {
+            double BmBy[9];
+            recovered_jac(pose, sb, v, rp, vb, gp, sJ, BmBy);
+            for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) { Jr[a * 21 + 15 + b] += sJ[a * 6 + b]; Jr[a * 21 + b] += sJ[36 + a * 6 + b]; }
+            for (int a = 0; a < 9; a++) Jr[(6 + a) * 21 + 6 + a] += 1.0;
+            for (int a = 0; a < 2; a++) for (int b = 0; b < 3; b++) Jr[(15 + a) * 21 + 18 + b] += BmBy[a * 3 + b];
+            for (int a = 0; a < 3; a++) Jr[(17 + a) * 21 + 15 + a] += 1.0;
+            for (int b = 0; b < 3; b++) Jr[20 * 21 + 18 + b] += BmBy[6 + b];
+        }
     }
     SYNC();
     if constexpr (PART == 0) for (int e = t; e < 441; e += MT) { ws[e] = Lp[e]; ws[448 + e] = Jr[e]; }
     MSTAMP(5);
+    if constexpr (PART == 3) {                       // the eigen-decomposition by the four wavefronts
+        for (int e = t; e < 441; e += NTH) M2[e] = Lp[e];
+        jacobi4<21>(M2, Vv, t);
+        if (t < 21) { const double ev = M2[t * 21 + t]; wv[t] = ev; keep[t] = ev > d.alpha_cut; }
+        SYNC();
+        MSTAMP(6);
+    }
     if constexpr (PART == 2) {                       // one launch: the eigen-decomposition by this wavefront
         for (int e = t; e < 441; e += MT) M2[e] = Lp[e];
         SYNC();
@@ -811,51 +927,68 @@ __global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
     if constexpr (PART != 0) {
     {
         double *Sg = Wk, *Xi = Wk + 100, *Xall = M1;             // Xall: 21x21 block-diagonal information (M1 is free now)
-        for (int e = t; e < 441; e += MT) Xall[e] = 0.0;
+        for (int e = t; e < 441; e += NTH) Xall[e] = 0.0;
         SYNC();
         // the five recovered blocks: relpose rows 0..5, VB rows 6..14, roll-pitch 15..16, |position| 17..19, yaw 20
-#define RECOVER(R0, NR, DST)                                                                        \
-        do {                                                                                        \
-            w_project_cov(Jr + (R0) * 21, (NR), 21, Vv, wv, keep, JU, Sg, t);                       \
-            w_inv(Sg, (NR), Xi, Wk + 300, piv, t);                                                  \
-            for (int e = t; e < (NR) * (NR); e += MT) Xall[((R0) + e / (NR)) * 21 + (R0) + e % (NR)] = Xi[e]; \
-            SYNC();                                                                                 \
-            if ((DST) != nullptr) {                                                                 \
-                w_chol_upper(Xi, (NR), Sg, Wk + 200, t);                                            \
-                for (int e = t; e < (NR) * (NR); e += MT) (DST)[e] = Sg[e];                         \
-                SYNC();                                                                             \
-            }                                                                                       \
+        // (WV: on one wavefront, lane index TT, with its own scratch -- projection JUp, Sgp / Xip, inverse Wp, Cholesky Lp_, pivot PV)
+#define RECOVER_ON(WV, TT, R0, NR, DST, JUp, Sgp, Xip, Wp, Lp_, PV)                                                     \
+        do {                                                                                                            \
+            w_project_cov<MT, WV>(Jr + (R0) * 21, (NR), 21, Vv, wv, keep, (JUp), (Sgp), (TT));                          \
+            w_inv<MT, WV>((Sgp), (NR), (Xip), (Wp), (PV), (TT));                                                        \
+            for (int e = (TT); e < (NR) * (NR); e += MT) Xall[((R0) + e / (NR)) * 21 + (R0) + e % (NR)] = (Xip)[e];    \
+            tsync<WV>();                                                                                                \
+            if ((DST) != nullptr) {                                                                                     \
+                w_chol_upper<MT, WV>((Xip), (NR), (Sgp), (Lp_), (TT));                                                  \
+                for (int e = (TT); e < (NR) * (NR); e += MT) (DST)[e] = (Sgp)[e];                                       \
+                tsync<WV>();                                                                                            \
+            }                                                                                                           \
         } while (0)
+#define RECOVER(R0, NR, DST) RECOVER_ON(false, t, R0, NR, DST, JU, Sg, Xi, Wk + 300, Wk + 200, piv)
         double *const no_dst = nullptr;
-        RECOVER(0, 6, rp.sqrt_info);
-        RECOVER(6, 9, vb.sqrt_info);
-        RECOVER(15, 2, gp.sqrt_info);
-        RECOVER(17, 3, no_dst);
-        RECOVER(20, 1, no_dst);
+        if constexpr (PART == 3) {
+            // three at a time: each block reads Jr, Vv, wv, keep and writes its own diagonal block of Xall and its own rows of the
+            // projection scratch (the row counts sum to 21: JU partitions by the first row).  The 9-row block keeps the scratch
+            // layout in Wk; the others take slices of M2, which is dead between the eigen-decomposition and A below.
+            if (wid == 0) RECOVER_ON(true, lane, 6, 9, vb.sqrt_info, JU + 6 * 21, Sg, Xi, Wk + 300, Wk + 200, piv);
+            else if (wid == 1) RECOVER_ON(true, lane, 0, 6, rp.sqrt_info, JU, M2, M2 + 36, M2 + 72, M2 + 144, piv + 1);
+            else if (wid == 2) {
+                RECOVER_ON(true, lane, 15, 2, gp.sqrt_info, JU + 15 * 21, M2 + 200, M2 + 210, M2 + 220, M2 + 240, piv + 2);
+                RECOVER_ON(true, lane, 17, 3, no_dst, JU + 17 * 21, M2 + 200, M2 + 210, M2 + 220, M2 + 240, piv + 2);
+                RECOVER_ON(true, lane, 20, 1, no_dst, JU + 20 * 21, M2 + 200, M2 + 210, M2 + 220, M2 + 240, piv + 2);
+            }
+            SYNC();
+        } else {
+            RECOVER(0, 6, rp.sqrt_info);
+            RECOVER(6, 9, vb.sqrt_info);
+            RECOVER(15, 2, gp.sqrt_info);
+            RECOVER(17, 3, no_dst);
+            RECOVER(20, 1, no_dst);
+        }
 #undef RECOVER
+#undef RECOVER_ON
         MSTAMP(7);
         // zero test / KLD (estimator.cpp:1519-1534): A = (Jr U)^T X (Jr U) over the kept eigenpairs vs D
         int rank = 0; for (int k = 0; k < 21; k++) rank += keep[k];
         double *JUa = Wk, *XJU = JU, *A = M2;            // (Jr is dead once JUa exists, the projection scratch JU already is)
-        for (int e = t; e < 21 * 21; e += MT) {
+        for (int e = t; e < 21 * 21; e += NTH) {
             const int a = e / 21, k = e % 21; double s = 0;
             for (int c = 0; c < 21; c++) s += Jr[a * 21 + c] * Vv[c * 21 + k];
             JUa[e] = s;                                   // all 21 columns; kept ones selected below
         }
         SYNC();
-        w_mm(Xall, JUa, XJU, 21, 21, 21, t);
-        for (int e = t; e < 441; e += MT) { const int a = e / 21, b = e % 21; double s = 0; for (int k = 0; k < 21; k++) s += JUa[k * 21 + a] * XJU[k * 21 + b]; A[e] = s; }
+        w_mm<NTH>(Xall, JUa, XJU, 21, 21, 21, t);
+        for (int e = t; e < 441; e += NTH) { const int a = e / 21, b = e % 21; double s = 0; for (int k = 0; k < 21; k++) s += JUa[k * 21 + a] * XJU[k * 21 + b]; A[e] = s; }
         SYNC();
         // restrict A to kept indices (rank x rank) in Wk+1000.. and evaluate trace / determinants
         double *Ak = Vv;                                  // (Vv was consumed by JUa above)
         if (t < 21) { int c = 0; for (int k = 0; k < t; k++) c += keep[k]; kpos[t] = c; }     // position of a kept index among the kept ones
         SYNC();
-        for (int e = t; e < 441; e += MT) {
+        for (int e = t; e < 441; e += NTH) {
             const int a = e / 21, b = e % 21;
             if (keep[a] && keep[b]) Ak[kpos[a] * rank + kpos[b]] = A[e];
         }
         SYNC();
-        const double ldA = w_logdet_spd(Ak, rank, JU, t);
+        const double ldA = w_logdet_spd<NTH>(Ak, rank, JU, t);
         if (t == 0) {
             double tr = 0, ldinv = 0; int ia = 0;
             for (int a = 0; a < 21; a++) if (keep[a]) { tr += Ak[ia * rank + ia] / wv[a]; ldinv += log(1.0 / wv[a]); ia++; }
@@ -868,6 +1001,7 @@ __global__ __launch_bounds__(MT) void k_marg_bwd(DevBatch d) {
 template __global__ void k_marg_bwd<0>(DevBatch);
 template __global__ void k_marg_bwd<1>(DevBatch);
 template __global__ void k_marg_bwd<2>(DevBatch);
+template __global__ void k_marg_bwd<3>(DevBatch);
 
 // ------------------------------------------------------------------------------------------
 // Estimator::initFactorGraph, the part after its ceres::Solve (src/estimator.cpp:744-999): build the first prior

@@ -118,10 +118,22 @@ __global__ __launch_bounds__(256) void k_step_control(DevBatch d) {
 
 // ------------------------------------------------------------------------------------------
 // after the solve: update() of every prior (estimator.cpp:1133-1144), then double2vector (:518-594)
-__global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
-    // one wavefront per window: lane roles for the prior updates, lane per frame for double2vector, lanes over
-    // the landmarks for the depths
-    const int w = blockIdx.x, lane = threadIdx.x;
+// NT = 64: one wavefront per window, lane roles for the prior updates (lane 0 Linear9, lane 1 the SE3 prior, lanes 2-31 the
+// relative poses, lanes 32-63 roll / pitch): the wavefront runs the four diverging so3_log / so3_exp chains one after another.
+// NT = 256: a wavefront per role (0: Linear9 and the SE3 prior, 1: relative poses, 2: roll / pitch, 3: the extrinsic of part 2),
+// so the chains run side by side; lane per frame for double2vector and lanes over the landmarks for the depths, over all NT.
+// The arithmetic of every role and entry is the same: the two forms give the same bits.
+// clear_marg: also clear the window's marginalisation record (k_marg_clear's job, which both marginalisation kernels wait for)
+template <int NT>
+__global__ __launch_bounds__(NT, NT > 64 ? 4 : 1) void k_finalize(DevBatch d, int do_update, int clear_marg) {
+    // (NT = 256: at most 128 registers -- a batch of four windows per CU is then resident at once, not in two rounds)
+    const int w = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    // the role of this lane and its index / stride inside the role
+    constexpr bool WIDE = NT > 64;
+    const int role = WIDE ? t >> 6 : (lane < 2 ? 0 : lane < 32 ? 1 : 2);
+    const int rel0 = WIDE ? lane : lane - 2, rel_step = WIDE ? 64 : 30;
+    const int rp0 = WIDE ? lane : lane - 32, rp_step = WIDE ? 64 : 32;
+    const bool ex_lane = WIDE ? t == 192 : lane == 2;
     if (ISV_SEQ_IDLE(d, w)) return;
     const int N = d.N, v = d.Nvo - 1;
     const double *pose = d.pose + (size_t)w * N * 7, *sb = d.sb + (size_t)w * N * 9;
@@ -141,7 +153,7 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
     // ---- update() of the prior factors (pseudo-measurement shift), one lane each; they read the old Ps / Rs ----
     // (initFactorGraph creates its priors at the estimate and calls double2vector() only: do_update == 0)
     if (!do_update) {
-    } else if (lane == 0) {
+    } else if (role == 0 && lane == 0) {
         // Linear9Factor::update  linear9_factor.h:60-68
         isv_linear9_t &f = d.lin9[w];
         for (int k = 0; k < 3; k++) {
@@ -149,7 +161,7 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
             f.VB[3 + k] += sb[9 * v + 3 + k] - Bas[3 * v + k];
             f.VB[6 + k] += sb[9 * v + 6 + k] - Bgs[3 * v + k];
         }
-    } else if (lane == 1) {
+    } else if (role == 0 && lane == 1) {
         // SE3PriorFactor::update  se3_prior_factor.h:73-81
         isv_se3_prior_t &f = d.se3[w];
         Quat R0 = q_from_R(Rs), R1 = q_normalized(q_from_pose(pose));
@@ -158,9 +170,9 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
         for (int k = 0; k < 3; k++) f.t[k] += pose[k] - Ps[k];
         q_to_R(so3_exp(dR), E); m3_mul(f.R, E, Rn);
         for (int k = 0; k < 9; k++) f.R[k] = Rn[k];
-    } else if (lane < 32) {
+    } else if (role == 1) {
         // RelativePoseFactor::update (solver overload)  relative_pose_factor.h:103-117
-        for (int i = lane - 2; i < d.Nvo - 1; i += 30) {
+        for (int i = rel0; i < d.Nvo - 1; i += rel_step) {
             isv_relpose_t &f = d.relpose[(size_t)w * (d.Nvo - 1) + i];
             const double *PSi = pose + 7 * i, *PSj = pose + 7 * (i + 1);
             const double *ti = Ps + 3 * i, *tj = Ps + 3 * (i + 1), *Ri = Rs + 9 * i, *Rj = Rs + 9 * (i + 1);
@@ -181,9 +193,9 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
             q_to_R(so3_exp(ww), E); m3_mul(f.delta_R, E, T); for (int k = 0; k < 9; k++) f.delta_R[k] = T[k];
             q_to_R(so3_exp(lgj), E); m3_mul(f.delta_R, E, T); for (int k = 0; k < 9; k++) f.delta_R[k] = T[k];
         }
-    } else {
+    } else if (role == 2) {
         // RollPitchFactor::update  rollpitch_factor.h:78-83
-        for (int m = lane - 32; m < d.n_rp[w]; m += 32) {
+        for (int m = rp0; m < d.n_rp[w]; m += rp_step) {
             isv_rollpitch_t &f = d.rollpitch[(size_t)w * d.max_rp + m];
             const int idx = f.index;
             Quat R0 = q_from_R(Rs + 9 * idx), R1 = q_normalized(q_from_pose(pose + 7 * idx));
@@ -194,13 +206,13 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
     }
     __syncthreads();                       // every update has read the old window states and written its prior
     // ---- double2vector, part 2 ----------------------------------------------------------------
-    if (lane == 0) {
+    if (t == 0) {
         double tt[3];
         m3v(rot_diff, d.lin9[w].VB + 6, tt); for (int k = 0; k < 3; k++) d.lin9[w].VB[6 + k] = tt[k];     // :549 (gyro-bias slot)
-    } else if (lane == 1) {
+    } else if (t == 1) {
         double Rn[9];
         m3_mul(rot_diff, d.se3[w].R, Rn); for (int k = 0; k < 9; k++) d.se3[w].R[k] = Rn[k];               // :550
-    } else if (lane == 2) {
+    } else if (ex_lane) {
         // tic / ric <- para_Ex_Pose (:577-586); when the extrinsic is estimated the solved block is the pseudo-frame's
         // pose, which also becomes d.ex (MargForward linearises at it, and the caller reads para_Ex_Pose from it)
         double *exw = d.ex + (size_t)w * 7;
@@ -209,7 +221,7 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
         q_to_R(q_from_pose(exw), d.ric + (size_t)w * 9);
     }
     const double p0[3] = {pose[0], pose[1], pose[2]};
-    for (int i = lane; i < d.Nr; i += 64) {            // (the real frames: the pseudo-frame is not a body pose)
+    for (int i = t; i < d.Nr; i += NT) {               // (the real frames: the pseudo-frame is not a body pose)
         double Ri[9], dd[3], tt[3], Ro[9];
         q_to_R(q_normalized(q_from_pose(pose + 7 * i)), Ri);
         m3_mul(rot_diff, Ri, Ro);
@@ -220,12 +232,18 @@ __global__ __launch_bounds__(64) void k_finalize(DevBatch d, int do_update) {
         m3v(rot_diff, sb + 9 * i, tt);
         for (int k = 0; k < 3; k++) { Vs[3 * i + k] = tt[k]; Bas[3 * i + k] = sb[9 * i + 3 + k]; Bgs[3 * i + k] = sb[9 * i + 6 + k]; }
     }
-    for (int l = d.lm_off[w] + lane; l < d.lm_off[w + 1]; l += 64) {        // FeatureManager::setDepth :145-163
+    for (int l = d.lm_off[w] + t; l < d.lm_off[w + 1]; l += NT) {        // FeatureManager::setDepth :145-163
         const double dep = 1.0 / d.lam[l];
         d.depth[l] = dep;
         d.solve_flag[l] = (dep < 0 || dep > 10) ? 2 : 1;
     }
+    if (clear_marg) {                      // (as k_marg_clear: padding included, so that downloads are deterministic)
+        double *z = reinterpret_cast<double *>(&d.marg[w]);
+        for (int e = t; e < (int)(sizeof(isv_marg_result_t) / sizeof(double)); e += NT) z[e] = 0.0;
+    }
 }
+template __global__ void k_finalize<64>(DevBatch, int, int);
+template __global__ void k_finalize<256>(DevBatch, int, int);
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -315,6 +333,7 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     hc.no_split = getenv("ISV_NO_SPLIT") != nullptr;
     hc.no_update = getenv("ISV_DEBUG_NO_UPDATE") != nullptr; hc.no_pose_dogleg = getenv("ISV_NO_POSE_DOGLEG") != nullptr;
     hc.marg_one_kernel = getenv("ISV_MARG_ONE_KERNEL") != nullptr; hc.marg_split = getenv("ISV_MARG_SPLIT") != nullptr;
+    hc.tail_one_wave = getenv("ISV_TAIL_ONE_WAVE") != nullptr;
     int dev0_ = 0;
     HCHK(hipGetDevice(&dev0_));
     if (hipDeviceGetAttribute(&hc.n_cus, hipDeviceAttributeMultiprocessorCount, dev0_) != hipSuccess) { (void)hipGetLastError(); hc.n_cus = 0; }
@@ -597,22 +616,35 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     }
     if (d.init_mode) {                     // Estimator::initFactorGraph: first priors from the solved estimate, then double2vector
         hipLaunchKernelGGL(k_init_priors, dim3(d.B), dim3(64), 0, st, d, d.init_scratch, d.init_per_window, d.init_kld);
-        hipLaunchKernelGGL(k_finalize, dim3(d.B), dim3(64), 0, st, d, 0);
+        if (hc.tail_one_wave) hipLaunchKernelGGL(k_finalize<64>, dim3(d.B), dim3(64), 0, st, d, 0, 0);
+        else hipLaunchKernelGGL(k_finalize<256>, dim3(d.B), dim3(256), 0, st, d, 0, 0);
         HCHK(hipGetLastError());
         return ISV_OK;
     }
-    hipLaunchKernelGGL(k_finalize, dim3(d.B), dim3(64), 0, st, d, hc.no_update ? 0 : 1);
-    // MargForward and MargBackward are independent: run them side by side.  The longer one (backward, 270 us per window against
-    // 110) goes on the main stream so that it is dispatched FIRST: four workgroups of each per CU do not fit the LDS together
-    // (4 x 27 KB + 4 x 19 KB > 160 KB), and whichever kernel arrives second runs its last workgroups after the first one's.
-    hipLaunchKernelGGL(k_marg_clear, dim3(d.B), dim3(64), 0, st, d);
+    // The tail is bound by the window's latency (the GPU is almost idle: a wavefront per window and SIMD in the one-wavefront
+    // forms), so k_finalize and MargBackward give a window four wavefronts and run its independent serial chains side by side;
+    // the marginalisation record is cleared at the end of k_finalize (ISV_TAIL_ONE_WAVE: the one-wavefront forms and k_marg_clear).
+    if (hc.tail_one_wave) {
+        hipLaunchKernelGGL(k_finalize<64>, dim3(d.B), dim3(64), 0, st, d, hc.no_update ? 0 : 1, 0);
+        hipLaunchKernelGGL(k_marg_clear, dim3(d.B), dim3(64), 0, st, d);
+    } else hipLaunchKernelGGL(k_finalize<256>, dim3(d.B), dim3(256), 0, st, d, hc.no_update ? 0 : 1, 1);
+    // MargForward and MargBackward are independent: run them side by side.  The longer one (backward) goes on the main stream
+    // so that it is dispatched FIRST: whichever kernel arrives second runs its last workgroups after the first one's when four
+    // workgroups of each per CU do not fit together.  They do fit: LDS 4 x 24.4 KB (k_marg_bwd<3>) + 4 x 14.1 KB (k_marg_fwd<64>)
+    // of 160 KB, registers 4 x 80 + 160 of a SIMD's 512 (k_marg_bwd<3> is held to 80 by its launch bounds).
+    // Measured, 1024 windows of 11 frames / 300 landmarks, per launch (rocprofv3 kernel trace of the benchmark; the one-wavefront
+    // tail first): k_finalize + k_marg_clear 37.5 + 4.7 -> k_finalize<256> 31.8 us; MargBackward 307 (k_marg_bwd<2>) -> 221 us
+    // (k_marg_bwd<3>; per window, in-kernel stamps: build 30.5 -> 25.1, eigen-decomposition 179 -> 104, projections 31 -> 16,
+    // KLD 26 -> 18); k_marg_fwd<64> beside it 148 -> 201 us and still ends 13 us before it; k_finalize's start to the later end
+    // 357 -> 259 us; step 5.146 -> 5.046 ms.  One window 1.59 -> 1.54 ms, 128 windows 1.88 -> 1.85 ms: the four-wavefront launch
+    // is the default for every batch size.
     HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
-    // a batch that leaves SIMDs idle (one wavefront per window: B < 4 n_cus) is latency bound and takes the four-wavefront
-    // eigen-decomposition (B = 1 / 64 / 256 / 512: 1.95 / 2.27 / 2.47 / 3.16 ms against 1.98 / 2.35 / 2.55 / 3.25); once
-    // every SIMD holds a window the phase is instruction-issue bound and the two forms tie (B = 1024: 5.75 ms either way);
-    // beyond that the one launch is kept
+    // The one-wavefront forms (ISV_TAIL_ONE_WAVE, and what ISV_MARG_ONE_KERNEL / ISV_MARG_SPLIT force): a batch that leaves SIMDs
+    // idle (one wavefront per window: B < 4 n_cus) takes the four-wavefront eigen-decomposition as a launch of its own (B = 1 /
+    // 64 / 256 / 512: 1.95 / 2.27 / 2.47 / 3.16 ms against 1.98 / 2.35 / 2.55 / 3.25), beyond that the one launch <2>
     const bool marg_one = hc.marg_one_kernel || (!hc.marg_split && hc.cap_batch > 3 * (size_t)hc.n_cus);     // (per handle: the two forms sum their convergence test in different orders)
-    if (marg_one) hipLaunchKernelGGL(k_marg_bwd<2>, dim3(d.B), dim3(64), 0, st, d);
+    if (!hc.tail_one_wave && !hc.marg_one_kernel && !hc.marg_split) hipLaunchKernelGGL(k_marg_bwd<3>, dim3(d.B), dim3(256), 0, st, d);
+    else if (marg_one) hipLaunchKernelGGL(k_marg_bwd<2>, dim3(d.B), dim3(64), 0, st, d);
     else {
         hipLaunchKernelGGL(k_marg_bwd<0>, dim3(d.B), dim3(64), 0, st, d);
         hipLaunchKernelGGL(k_marg_jacobi<21>, dim3(d.B), dim3(256), 0, st, d);
