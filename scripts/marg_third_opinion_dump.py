@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import isvins_loader; isvins_loader.load()
 import numpy as np
 from isvins_amd import abi, backend
+import marg_highprec as mh
 import oracle_lib
 import sequence_harness as sh
 import test_sequence_long as tl
@@ -59,10 +60,6 @@ class Collect(sh.OracleSolver):
         return s, m
 
 
-def raw(struct):
-    return np.frombuffer(bytes(struct), dtype=np.uint8).copy()
-
-
 def main():
     oracle = oracle_lib.load()
     cfg = abi.make_config(N, NVO, max_landmarks=1000, max_obs=1000 * N, max_batch=1)
@@ -93,13 +90,9 @@ def main():
         out[p + "same_input_rel"] = info_rel(mg, mo)
         out[p + "input_mismatch"] = max(np.abs(g.para_Pose - o.para_Pose).max(), np.abs(g.para_SpeedBias - o.para_SpeedBias).max())
         # what MargForward / MargBackward read (oracle side's values; src/estimator.cpp:1149-1539)
-        v = NVO
-        out[p + "pose"] = o.para_Pose[[0, 1, v - 1, v]].copy(); out[p + "sb"] = o.para_SpeedBias[[v - 1, v]].copy(); out[p + "ex"] = o.para_Ex_Pose.copy()
-        sel = [l for l in range(o.L) if o.lm_start_frame[l] == 0 and o.lm_obs_ptr[l + 1] - o.lm_obs_ptr[l] >= 2]
-        out[p + "lam"] = np.array([o.para_Feature[l] for l in sel])
-        out[p + "pts"] = np.array([[o.obs_point[o.lm_obs_ptr[l]], o.obs_point[o.lm_obs_ptr[l] + 1]] for l in sel]).reshape(len(sel), 2, 3)
-        out[p + "pose_prior"] = raw(o.pose_prior); out[p + "vb_prior"] = raw(o.vb_prior); out[p + "relpose0"] = raw(o.relpose[0])
-        out[p + "imu"] = raw(o.imu[v - 1])
+        ins = mh.inputs_from_window(cfg0, o)
+        sel = mh.selected_landmarks(o)
+        out.update({p + k: a for k, a in ins.items() if k not in ("alpha", "gravity", "proj_sqrt_info")})      # (those three: once, above)
         for side, m in (("gpu", mg), ("oracle", mo)):
             for name, kk in FACTORS + (("combined_relpose", 6),):
                 f = m.combined.relative_pose if name == "combined_relpose" else getattr(m, name)

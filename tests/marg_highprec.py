@@ -1,7 +1,8 @@
 """MargForward / MargBackward (src/estimator.cpp:1149-1352 / :1354-1539) recomputed at 40 digits in mpmath -- a THIRD opinion beside
 the CPU oracle (double, LU / cyclic Jacobi) and the HIP kernels (double, closed-form landmark elimination / Gauss-Jordan / parallel
 Jacobi).  Test infrastructure: tests/test_marg_third_opinion.py feeds it the inputs both routines read, as
-recorded in tests/golden/marg_third_opinion.npz by scripts/marg_third_opinion_dump.py.
+recorded in tests/golden/marg_third_opinion.npz by scripts/marg_third_opinion_dump.py; tests/test_marg_highprec.py (the oracle) and
+tests/test_gpu_marg_highprec.py (the kernels) feed it live windows through inputs_from_window and measure against e64_* / float64_limit.
 
 Every residual is the one tests/test_highprec_jacobians.py writes down from the reference's Evaluate(); Jacobians of the factors whose
 analytic blocks are exact derivatives (ProjectionFactor, SE3Prior, RelativePose, RollPitch, Yaw) are central differences through the
@@ -180,6 +181,7 @@ def marg_forward(z, p, alpha):
     n0 = len(lam)
     S12 = mp.zeros(12, 12)                       # the two pose blocks with the landmarks eliminated (each landmark is a 1 x 1 block)
     L12 = mp.zeros(12, 12)                       # ... and without (Lam_rp, :1240: the reference takes the top-left corner of Lam as it is)
+    Jlm = []                                     # per landmark: its 2 x 13 Jacobian [T1 | T0 | inverse depth]
     for m in range(n0):
         l, pi, pj = mp.mpf(float(lam[m])), mpv(pts[m, 0]), mpv(pts[m, 1])
         Ji = jac_pose_mp(lambda x: proj_res(x, pose1, ex, l, pi, pj, sq), pose0, 2)
@@ -188,6 +190,7 @@ def marg_forward(z, p, alpha):
         J = mp.zeros(2, 12)
         set_block(J, 0, 0, Jj); set_block(J, 0, 6, Ji)
         Hpp, c, dl = J.T * J, J.T * Jl, (Jl.T * Jl)[0, 0]
+        Jlm.append([[float(J[a, b]) for b in range(12)] + [float(Jl[a, 0])] for a in range(2)])
         L12 += Hpp
         S12 += Hpp - c * c.T / dl
     prior = struct_of(abi.isv_se3_prior_t, z[p + "pose_prior"])
@@ -203,6 +206,9 @@ def marg_forward(z, p, alpha):
     set_block(J, 0, 0, Jj); set_block(J, 0, 6, Ji)
     S12 = S12 + J.T * J
     L12 = L12 + J.T * J
+    P12 = mp.zeros(12, 12)                       # the part of both that is not a landmark's: the pose prior and the relative-pose factor
+    add_block(P12, 6, 6, Jp.T * Jp)
+    P12 = P12 + J.T * J
     # (i) the pose-graph edge (:1240-1283): measurement from the current poses, J = [J_i | J_j] against Lam_rp ordered [T1 | T0] (as the reference has it)
     Qi, Qj = q_from_pose(pose0), q_from_pose(pose1)
     d = [pose1[k] - pose0[k] for k in range(3)]
@@ -232,6 +238,10 @@ def marg_forward(z, p, alpha):
     out["forward_pose_prior"] = mp.inverse(covi)
     E = mp.eigsy(Lprior, eigvals_only=True)
     out["_fwd_rank"] = rank
+    out["_fwd_eigs"] = [float(e) for e in E]
+    # what e64_forward starts from: the landmark Jacobians, the landmark-free part, the two 12 x 12 blocks and the stacked Jacobians
+    out["_fwd_Jlm"] = np.array(Jlm).reshape(n0, 2, 13)
+    out["_fwd_P12"], out["_fwd_S12"], out["_fwd_L12"], out["_fwd_Jg"], out["_fwd_Jr"] = P12, S12, L12, Jg, Jr
     out["_fwd_cond"] = float(max(E) / min(E)) if min(E) > 0 else float("inf")
     out["_fwd_n_landmarks"] = n0
     return out
@@ -320,6 +330,8 @@ def marg_backward(z, p, alpha):
     out = {"backward_relpose": project_info(sub(Jr, 0, 6, 0, 21), U, Dv), "backward_vb": project_info(sub(Jr, 6, 15, 0, 21), U, Dv),
            "backward_rollpitch": project_info(sub(Jr, 15, 17, 0, 21), U, Dv)}
     out["_bwd_rank"] = len(Dv)
+    out["_bwd_Lam"], out["_bwd_Jr"] = Lam, Jr        # what e64_backward starts from
+    out["_bwd_kept"] = [float(e) for e in Dv]
     out["_bwd_eigs"] = [float(e) for e in Eall]
     out["_bwd_cond_kept"] = float(max(Dv) / min(Dv))
     return out
@@ -327,3 +339,80 @@ def marg_backward(z, p, alpha):
 
 def to_np(M):
     return np.array([[float(M[a, b]) for b in range(M.cols)] for a in range(M.rows)])
+
+
+def raw(struct):
+    return np.frombuffer(bytes(struct), dtype=np.uint8).copy()
+
+
+def selected_landmarks(w):
+    """the landmarks MargForward marginalises: hosted in frame 0, seen at least twice (src/estimator.cpp:1166-1178)"""
+    return [l for l in range(w.L) if w.lm_start_frame[l] == 0 and w.lm_obs_ptr[l + 1] - w.lm_obs_ptr[l] >= 2]
+
+
+def inputs_from_window(cfg, w):
+    """what marg_forward / marg_backward read (src/estimator.cpp:1149-1539), from a window as a solve left it: the para_* arrays and
+    the priors after update().  The keys are the fixture's without its per-window prefix: call the two routines with p = ""."""
+    v = cfg.n_vo
+    sel = selected_landmarks(w)
+    return dict(pose=w.para_Pose[[0, 1, v - 1, v]].copy(), sb=w.para_SpeedBias[[v - 1, v]].copy(), ex=w.para_Ex_Pose.copy(),
+                lam=np.array([w.para_Feature[l] for l in sel]),
+                pts=np.array([[w.obs_point[w.lm_obs_ptr[l]], w.obs_point[w.lm_obs_ptr[l] + 1]] for l in sel]).reshape(len(sel), 2, 3),
+                pose_prior=raw(w.pose_prior), vb_prior=raw(w.vb_prior), relpose0=raw(w.relpose[0]), imu=raw(w.imu[v - 1]),
+                alpha=cfg.alpha, gravity=np.array(cfg.gravity[:]), proj_sqrt_info=np.array(cfg.proj_sqrt_info[:]))
+
+
+# ---- the float64 yardstick: the same algebra in numpy from the 40-digit intermediates rounded to double -----------------------
+def rel(A, X):
+    """max-norm distance of A from X, relative to X's largest entry"""
+    return float(np.abs(A - X).max() / np.abs(X).max())
+
+
+def _schur64(S, n):
+    """S[:n, :n] - S[:n, n:] S[n:, n:]^-1 S[n:, :n] by a Cholesky solve"""
+    A, B, D = S[:n, :n], S[:n, n:], S[n:, n:]
+    c = np.linalg.cholesky(D)
+    Y = np.linalg.solve(c, B.T)
+    return A - Y.T @ Y
+
+
+def _project64(Jk, U, Dv):
+    JU = Jk @ U
+    return np.linalg.inv((JU / Dv) @ JU.T)
+
+
+def float64_limit(Lam, kept):
+    """the cancellation bound of a double-precision Schur complement + eigen-truncation: entries of size max|Lam| are subtracted down
+    to a marginal whose smallest kept eigenvalue is min(kept), and the projections divide by it"""
+    return 2.0 ** -52 * float(np.abs(np.asarray(Lam, float)).max()) / float(min(kept))
+
+
+def e64_backward(b, alpha):
+    """{factor: distance of a plain float64 MargBackward from the 40-digit one `b` (marg_backward's result)}"""
+    Lam, Jr = to_np(b["_bwd_Lam"]), to_np(b["_bwd_Jr"])
+    Lp = _schur64(Lam, 21)
+    E, Q = np.linalg.eigh(0.5 * (Lp + Lp.T))
+    keep = E > float(alpha)
+    U, Dv = Q[:, keep], E[keep]
+    rows = {"backward_relpose": slice(0, 6), "backward_vb": slice(6, 15), "backward_rollpitch": slice(15, 17)}
+    return {name: rel(_project64(Jr[r], U, Dv), to_np(b[name])) for name, r in rows.items()}
+
+
+def e64_forward(f, alpha):
+    """{forward_pose_prior, combined_relpose, covRel: distance of a plain float64 MargForward from the 40-digit one `f`}: the landmarks
+    eliminated in closed form from their Jacobians as marg_forward does, then the 6 x 6 Schur complement, eigh and the projection"""
+    P12, Jg, Jr = to_np(f["_fwd_P12"]), to_np(f["_fwd_Jg"]), to_np(f["_fwd_Jr"])
+    S12, L12 = P12.copy(), P12.copy()
+    for JJ in f["_fwd_Jlm"]:
+        J, Jl = JJ[:, :12], JJ[:, 12]
+        Hpp, c, dl = J.T @ J, J.T @ Jl, Jl @ Jl
+        L12 += Hpp
+        S12 += Hpp - np.outer(c, c) / dl
+    Jpinv = Jg.T @ np.linalg.inv(Jg @ Jg.T)
+    Om = Jpinv.T @ L12 @ Jpinv
+    out = {"combined_relpose": rel(Om, to_np(f["combined_relpose"])), "covRel": rel(np.linalg.inv(Om), to_np(f["covRel"]))}
+    Lp = _schur64(S12, 6)
+    E, Q = np.linalg.eigh(0.5 * (Lp + Lp.T))
+    keep = E > float(alpha)
+    out["forward_pose_prior"] = rel(_project64(Jr, Q[:, keep], E[keep]), to_np(f["forward_pose_prior"]))
+    return out

@@ -95,6 +95,7 @@ def check_marg(mo, mg, Nvo):
     """MargForward / MargBackward outputs.  The recovered factors' information matrices (sqrt_info^T
     sqrt_info) are compared, relative to their largest entry: 1e-6 (they go through an
     eigen-decomposition and several small inverses; the GPU uses Jacobi sweeps + Gauss-Jordan)."""
+    # (this 1e-6 is about twice the float64 limit of MargBackward on these windows, 5.5e-7: tests/test_gpu_marg_highprec.py holds each side to the exact answer)
     assert mg.valid == 1 and mg.n_marg_landmarks == mo.n_marg_landmarks
     for name, n in (("forward_pose_prior", 6), ("backward_relpose", 6), ("backward_vb", 9), ("backward_rollpitch", 2)):
         a, b = _info(getattr(mg, name).sqrt_info, n), _info(getattr(mo, name).sqrt_info, n)
