@@ -1,7 +1,12 @@
 """GPU parity of the batched visual-inertial alignment (k_visual_imu_align, is-vins_amd/csrc/isv_initial.h) against the CPU
 restatement tests/native/isv_init_oracle.c, and batch against single.  Tolerances: status identical; repropagated deltas
 1e-12; window states 1e-6 relative; g and s 1e-8 relative; a problem's result in a batch of 1 / 64 / 1024 bitwise equal to
-the same problem solved alone."""
+the same problem solved alone.
+
+The tolerances are round numbers, not derived ones.  What float64 allows on each field, per case, and how far the kernel is from the exact
+answer of its own equations is tests/test_gpu_align_highprec.py (model and limits: tests/align_highprec.py; figures: DESIGN.md section 11).
+Its limits lie 100 to 1e5 times below the tolerances here, and it asserts that the fields before the first atan2 are bytewise the
+restatement's; the tolerances here stay as the coarse guard on every case, the singular and refused ones included."""
 import ctypes as C
 
 import numpy as np
