@@ -6,8 +6,8 @@
  * one call (MI355X).  A sequence's tracker state, the image pyramid of its last `cur` image, stays on the device in a SLOT: the steady
  * state uploads one image and builds one pyramid per frame.
  *
- * Not here: goodFeaturesToTrack, setMask, rejectWithF and CLAHE (published frames only), and the host bookkeeping: the compaction
- * (reduceVector), track_cnt++, ids and the velocity map stay with the caller.
+ * Not here: setMask and goodFeaturesToTrack are isvins_detect.h, on this handle's slots; rejectWithF and CLAHE are nowhere yet; the
+ * host bookkeeping, that is the compaction (reduceVector), track_cnt++, ids and the velocity map, stays with the caller.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (video: lkpyramid.cpp; imgproc: pyramids.cpp; core: copy.cpp) and from
  * PinholeCamera.cc:461-521, :657-673.  OpenCV is not available to this project, so the restatement cannot be checked against it.  The

@@ -1,7 +1,8 @@
 // isv_init_launch.h -- the host side the batched stages share: the three initialisation stages on a backend handle
 // (isv_initial.hip, isv_sfm.hip, isv_relpose.hip), the loop-closure verification (isv_loop.hip), the loop detection
 // (isv_bow.hip), the keyframe extraction (isv_keyframe.hip) and the feature tracking (isv_tracker.hip), each of the four on its
-// own handle.
+// own handle.  (The feature detection, isv_detect.hip, runs on a tracker handle's stream and takes the argument checks from here;
+// its five timed sections need more events than run() has.)
 // A stage call packs its problems into one pageable upload block, launches one workgroup per problem on the caller's stream and
 // copies its outputs back, synchronously.  A stage file keeps what is its own: its header record and problem checks, the packing,
 // the kernel launch(es) and the post-processing of the outputs.

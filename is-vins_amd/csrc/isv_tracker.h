@@ -1,5 +1,6 @@
 // isv_tracker.h -- internal to the feature tracking (isv_tracker.hip), outside include/: the debug read-back of a slot's pyramids,
-// so that the tests report a wrong pyramid as a wrong pyramid rather than as wrong tracks.
+// so that the tests report a wrong pyramid as a wrong pyramid rather than as wrong tracks; and the tracker handle itself with its
+// slots, which the feature detection (isv_detect.hip) reads: a detector works on level 0 of a slot's resident pyramid.
 #pragma once
 #include "../../include/isvins_tracker.h"
 
@@ -14,4 +15,40 @@ int isv_internal_trk_read_level(isv_trk_t *h, int32_t slot, int32_t which, int32
 
 #ifdef __cplusplus
 }
+#endif
+
+#ifdef __HIPCC__
+#include "isv_init_launch.h"
+#include "isv_pinhole.h"
+
+constexpr int kTrkLevels = ISV_TRK_MAX_LEVEL + 1;
+
+struct TrkShape {                 // a pyramid's levels: sizes and packed offsets
+    int32_t lw[kTrkLevels], lh[kTrkLevels];
+    uint32_t lo[kTrkLevels];
+    int32_t nlev, pad;
+};
+
+struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0; };      // par: which of the slot's two buffers is resident
+
+struct isv_trk {
+    isv_trk_config_t cfg;
+    PinholeCam cam;
+    std::string err;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    InitSlot slot;                // the call's device block (grow-only), events and times
+    hipEvent_t kev = nullptr;     // before the upload
+    double upload_ms = 0, pack_ms = 0;
+    uint8_t *d_store = nullptr;   // [max_slots][2][slot_bytes]: the slots' pyramids
+    size_t slot_bytes = 0;        // a pyramid of max_width x max_height, rounded up to 256
+    std::vector<TrkSlot> slots;
+    std::vector<int32_t> named;   // [max_slots]: how many good items of the call name the slot (valid where stamp is the call's serial)
+    std::vector<int64_t> stamp;
+    int64_t serial = 0;
+    std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
+    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
+    // the store offset of a slot's buffer; level 0 of a pyramid is at its start
+    size_t store_off(int slot_i, int buf) const { return ((size_t)slot_i * 2 + buf) * slot_bytes; }
+};
 #endif

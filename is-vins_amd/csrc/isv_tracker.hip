@@ -34,17 +34,11 @@ namespace {
 constexpr int kLanes = 64;
 constexpr int kWin = ISV_TRK_WIN, kNWin = kWin * kWin, kSup = kWin + 1, kPatch = kWin + 3;   // 21, 441, 22, 24
 constexpr int kPerLane = (kNWin + kLanes - 1) / kLanes;                                       // 7
-constexpr int kLevels = ISV_TRK_MAX_LEVEL + 1;
+constexpr int kLevels = kTrkLevels;
 constexpr int kPW = 32, kPH = 16, kPThreads = 256;    // k_trk_pyrdown's output tile, its workgroup
 constexpr int kSrcW = 2 * kPW + 3, kSrcH = 2 * kPH + 3;
 constexpr int kCopyThreads = 256, kCopyBlocks = 32;   // k_trk_level0: blocks per image
 constexpr int kMaxSide = 8192, kMaxSlots = 65536, kMaxPoints = 65535;
-
-struct TrkShape {                 // a pyramid's levels: sizes and packed offsets
-    int32_t lw[kLevels], lh[kLevels];
-    uint32_t lo[kLevels];
-    int32_t nlev, pad;
-};
 
 struct TrkJob {                   // one pyramid to build: an uploaded image -> a slot buffer
     uint64_t src_off, dst_off;    // into the upload block's images; into the store
@@ -56,8 +50,6 @@ struct TrkItem {                  // one item that passed every check
     TrkShape s;
     int32_t np, pt_off, pad[2];
 };
-
-struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0; };      // par: which of the slot's two buffers is resident
 
 TrkShape make_shape(int W, int H) {
     TrkShape s;
@@ -74,26 +66,6 @@ TrkShape make_shape(int W, int H) {
 size_t shape_bytes(const TrkShape &s) { return (size_t)s.lo[s.nlev - 1] + (size_t)s.lw[s.nlev - 1] * s.lh[s.nlev - 1]; }
 
 }  // namespace
-
-struct isv_trk {
-    isv_trk_config_t cfg;
-    PinholeCam cam;
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    InitSlot slot;                // the call's device block (grow-only), events and times
-    hipEvent_t kev = nullptr;     // before the upload
-    double upload_ms = 0, pack_ms = 0;
-    uint8_t *d_store = nullptr;   // [max_slots][2][slot_bytes]: the slots' pyramids
-    size_t slot_bytes = 0;        // a pyramid of max_width x max_height, rounded up to 256
-    std::vector<TrkSlot> slots;
-    std::vector<int32_t> named;   // [max_slots]: how many good items of the call name the slot (valid where stamp is the call's serial)
-    std::vector<int64_t> stamp;
-    int64_t serial = 0;
-    std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
-    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
-    size_t store_off(int slot_i, int buf) const { return ((size_t)slot_i * 2 + buf) * slot_bytes; }
-};
 
 // BORDER_REFLECT_101 (cv::borderInterpolate), the general loop: always inside [0, len)
 __device__ __forceinline__ int trk_reflect(int p, int len) {
