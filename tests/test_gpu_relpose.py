@@ -3,7 +3,10 @@ tests/native/isv_relpose_oracle.c, batch against single, and initial_structure_f
 followed by initial_structure_batch.  Identical: status, l, per-candidate correspondence counts, RANSAC iterations and
 inliers, recoverPose counts and chosen solutions, the per-track masks; the parallax bitwise (the same sums in the same
 order).  relative_R / relative_T agree to 1e-9: the two run the same operations, and only the device and host libm can round
-solveCubic's acos / cos / pow apart by an ulp, which moves a model by about that much."""
+solveCubic's acos / cos / pow apart by an ulp, which moves a model by about that much.
+
+The restatement is the same text as the kernel's serial pieces; tests/test_gpu_relpose_highprec.py holds the kernel to an independent 40-digit
+reference instead, at 21 to 129 correspondences (every case here has 21 to 41) and at the chunk edges of the speculative RANSAC."""
 import numpy as np
 import pytest
 
