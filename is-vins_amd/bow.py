@@ -10,7 +10,7 @@ import functools
 
 import numpy as np
 
-from . import backend
+from . import _stage, backend
 
 ISV_BOW_OK, ISV_BOW_CAPACITY, ISV_BOW_INPUT, ISV_BOW_DUPLICATE = range(4)
 ISV_BOW_DETECT, ISV_BOW_ADD, ISV_BOW_QUERY = range(3)
@@ -63,13 +63,8 @@ class BowItem:
         c.brief = self.brief.ctypes.data_as(_u64p)
 
 
-_bound = False
-
-
+@_stage.bind_once("bow")
 def _bind(lib):
-    global _bound
-    if _bound:
-        return
     vp = C.c_void_p
     infop = C.POINTER(isv_bow_vocab_info_t)
     lib.isv_bow_vocab_check.argtypes = [C.c_char_p, C.c_size_t, infop]
@@ -82,7 +77,6 @@ def _bind(lib):
     lib.isv_bow_last_ms.argtypes = [vp, _f64p]
     lib.isv_bow_reset.argtypes = [vp, C.c_int32]
     lib.isv_bow_entries.argtypes = [vp, C.c_int32]
-    _bound = True
 
 
 def vocab_check(data, lib=None):
@@ -96,30 +90,15 @@ def vocab_check(data, lib=None):
     return lib.isv_bow_vocab_check(data, len(data), C.byref(info)), info
 
 
-class LoopDetector:
+class LoopDetector(_stage.StageHandle):
     """PoseGraph::detectLoop on the MI355X for n_databases sequences in lock step: one keyframe per database per call"""
+    PREFIX, N_MS = "isv_bow", 5
 
     def __init__(self, vocab, max_items=1, n_databases=1, max_features=2048, **kw):
-        self.lib = backend.load_library()
-        _bind(self.lib)
         self.cfg = make_config(max_items, n_databases, max_features, **kw)
-        self.h = C.c_void_p()
         vocab = bytes(vocab)
-        rc = self.lib.isv_bow_create(C.byref(self.cfg), vocab, len(vocab), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise backend.BackendError(f"isv_bow_create: {backend.STATUS.get(rc, rc)} (a valid vocabulary, a MI355X and the HIP extension are "
-                                       "required; there is no CPU path)")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.isv_bow_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(_bind, C.byref(self.cfg), vocab, len(vocab),
+                     why=" (a valid vocabulary, a MI355X and the HIP extension are required; there is no CPU path)")
 
     def detect_batch(self, items, vectors=False):
         """items: BowItem list -> isv_bow_result_t list; with vectors also (word_ids, word_weights), each a list of arrays [n_words]
@@ -133,9 +112,7 @@ class LoopDetector:
             vs = [np.full(max(it.c.n_features, 1), -2.0) for it in items]
             args = [(_u32p * max(n, 1))(*[a.ctypes.data_as(_u32p) for a in ws]), (_f64p * max(n, 1))(*[a.ctypes.data_as(_f64p) for a in vs])]
         rc = self.lib.isv_bow_detect_batch(self.h, n, ptrs, res, *args)
-        if rc != 0:
-            msg = self.lib.isv_bow_last_error(self.h)
-            raise backend.BackendError(f"isv_bow_detect_batch: {backend.STATUS.get(rc, rc)} {msg.decode() if msg else ''}")
+        self._check(rc, "isv_bow_detect_batch", with_last_error=True)
         out = list(res)[:n]
         if not vectors:
             return out
@@ -146,11 +123,7 @@ class LoopDetector:
 
     def last_ms(self):
         """(whole call, k_bow_transform, k_bow_score, k_bow_select, k_bow_append) milliseconds of the last successful call"""
-        ms = (C.c_double * 5)()
-        rc = self.lib.isv_bow_last_ms(self.h, ms)
-        if rc != 0:
-            raise backend.BackendError(f"isv_bow_last_ms: {backend.STATUS.get(rc, rc)}")
-        return tuple(ms)
+        return super().last_ms()
 
     def reset(self, db):
         if self.lib.isv_bow_reset(self.h, db) != 0:

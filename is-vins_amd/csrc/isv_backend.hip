@@ -29,7 +29,7 @@ extern "C" void isv_backend_destroy(isv_backend_t *h) {
     if (h->seq && h->seq_free) h->seq_free(h->seq);
     if (h->init_scratch) (void)hipFree(h->init_scratch);
     if (h->init_kld) (void)hipFree(h->init_kld);
-    for (InitSlot &s : h->init_slot) init_slot_free(s);
+    for (StageSlot &s : h->init_slot) stage_slot_free(s);
     for (void *p : h->allocs) (void)hipFree(p);
     for (void *p : h->hallocs) (void)hipHostFree(p);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);

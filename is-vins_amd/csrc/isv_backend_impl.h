@@ -16,20 +16,25 @@
         }                                                                                        \
     } while (0)
 
-// the batched initialisation stages (isv_init_launch.h runs them): isv_internal_visual_imu_align_batch (isv_initial.hip),
+// the batched initialisation stages (isv_stage_launch.h runs them): isv_internal_visual_imu_align_batch (isv_initial.hip),
 // isv_internal_sfm_batch (isv_sfm.hip), isv_internal_relpose_batch (isv_relpose.hip)
 enum { ISV_INIT_ALIGN, ISV_INIT_SFM, ISV_INIT_RELPOSE, ISV_INIT_STAGES };
-// a stage's state on the handle: its device block (grow-only, freed with the handle), its kernel events, its last call's times
-struct InitSlot {
+// a batched stage's state on its handle (isv_stage_launch.h): its device block (grow-only, freed with the handle), its events, its
+// last successful call's times.  The kernel sections' boundaries are consecutive events: k0, up to kStageMarks marks, k1.
+constexpr int kStageMarks = 3;
+enum { SE_BEGIN, SE_END, SE_K0, SE_EVENTS = SE_K0 + kStageMarks + 2 };
+struct StageSlot {
     void *d = nullptr; size_t cap = 0;
-    hipEvent_t ev[3] = {};        // before the kernels, after them, between two of them
-    double call_ms = 0, kernel_ms = 0, part_ms[2] = {};   // part_ms: each kernel of a two-kernel stage
+    hipEvent_t ev[SE_EVENTS] = {};
+    double call_ms = 0, upload_ms = 0, kernel_ms = 0, download_ms = 0;   // the whole call on the host; begin-k0, k0-k1, k1-end (0 unless
+                                                                         // the call records `end`: StageCall::time_download)
+    double part_ms[kStageMarks + 1] = {};                                // k0 through the marks to k1, interval by interval
 };
 // the slot's end: its block and events (the owning handle's device is selected)
-inline void init_slot_free(InitSlot &s) {
+static inline void stage_slot_free(StageSlot &s) {
     if (s.d) (void)hipFree(s.d);
     for (auto &e : s.ev) if (e) (void)hipEventDestroy(e);
-    s = InitSlot{};
+    s = StageSlot{};
 }
 
 // a block of buffers, laid out section by section: each starts 256-byte aligned (the kernels read every section by pointer)
@@ -81,7 +86,7 @@ struct isv_backend {
     double *init_scratch = nullptr, *init_kld = nullptr;   // initFactorGraph scratch, allocated on first use and kept
     size_t init_cap = 0;
     int sfm_ba_iters = 50;        // max_num_iterations of the SfM stage's BA (test hook, env ISV_DEBUG_SFM_BA_ITERS = 0..50, read at creation)
-    InitSlot init_slot[ISV_INIT_STAGES];   // the batched initialisation stages' blocks, events and times (isv_init_launch.h)
+    StageSlot init_slot[ISV_INIT_STAGES];   // the batched initialisation stages' blocks, events and times (isv_stage_launch.h)
     double last_ms[8] = {};
     int64_t last_counts[8] = {};
     hipGraphExec_t graph_exec = nullptr;    // ISV_GRAPH=1 (measurement hook): the captured launch chain of isv_batch_optimize

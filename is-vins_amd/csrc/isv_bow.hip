@@ -1,7 +1,7 @@
 // isv_bow.hip -- batched loop detection: PoseGraph::detectLoop / addKeyFrameIntoVoc for S sequences in lock step, one DBoW
 // database per sequence (include/isvins_bow.h has the contract, the reference lines, the arithmetic, the quirks B1..B4 and the
 // deviation; tests/native/isv_bow_oracle.c is the serial restatement the kernels are pinned to, bit for bit).  One packed upload,
-// four kernels, one download (isv_init_launch.h).  FP64, contraction off, no atomics: every sum has one fixed order.
+// four kernels, one download (isv_stage_launch.h).  FP64, contraction off, no atomics: every sum has one fixed order.
 //
 // k_bow_transform: one workgroup of four wavefronts per item.  A lane per feature descends the vocabulary, which lies on the
 // device breadth-first with a node's children contiguous in file order and the descriptors as two 16-byte planes (128-bit
@@ -22,7 +22,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_bow_vocab.h"
 
 namespace {
@@ -64,19 +64,12 @@ struct BwParams {
 
 }  // namespace
 
-struct isv_bow {
+struct isv_bow : StageHandle {
     isv_bow_config_t cfg;
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    InitSlot slot;                // the call's device block (grow-only), events and times
-    hipEvent_t kev[3] = {};       // between the four kernels
-    double part_ms[4] = {};
     void *d_vocab = nullptr;
     BwVocabDev vocab{};
     isv_bow_vocab_info_t info{};
     std::vector<BwDb> dbs;
-    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
 };
 
 __global__ void __launch_bounds__(kThreads) k_bow_transform(const BwHdr *__restrict__ hdrs, const BwVocabDev V, const uint64_t *__restrict__ feats,
@@ -362,12 +355,9 @@ extern "C" const char *isv_bow_last_error(const isv_bow_t *h) { return h ? h->er
 
 extern "C" void isv_bow_destroy(isv_bow_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
+    h->close();
     for (BwDb &d : h->dbs) db_free(d);
     if (h->d_vocab) (void)hipFree(h->d_vocab);
-    init_slot_free(h->slot);
-    for (auto &e : h->kev) if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -384,13 +374,7 @@ extern "C" int isv_bow_create(const isv_bow_config_t *c, const void *vocab_bytes
     isv_bow *h = new isv_bow();
     h->cfg = *c;
     h->info = v.info;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e == hipSuccess && ndev <= 0) e = hipErrorNoDevice;
-    if (e == hipSuccess) e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (auto &ev : h->kev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
+    hipError_t e = h->open();
     if (e == hipSuccess) {
         // the vocabulary block: [first_child | n_children | word_id | weight | word_weight | descriptor planes a, b]
         const size_t N = (size_t)v.info.n_nodes + 1, W = (size_t)v.info.n_words;
@@ -423,9 +407,7 @@ extern "C" int isv_bow_create(const isv_bow_config_t *c, const void *vocab_bytes
             if (e == hipSuccess) e = hipMemset(d.eptr, 0, sizeof(uint32_t));
         }
     }
-    if (e != hipSuccess) {
-        fprintf(stderr, "isv_bow_create: %s\n", hipGetErrorString(e));
-        (void)hipGetLastError();
+    if (stage_open_failed("isv_bow_create", e)) {
         isv_bow_destroy(h);
         return ISV_ERR_DEVICE;
     }
@@ -436,7 +418,7 @@ extern "C" int isv_bow_create(const isv_bow_config_t *c, const void *vocab_bytes
 extern "C" int isv_bow_last_ms(isv_bow_t *h, double out_ms[5]) {
     if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
     out_ms[0] = h->slot.call_ms;
-    for (int i = 0; i < 4; i++) out_ms[1 + i] = h->part_ms[i];
+    for (int i = 0; i < 4; i++) out_ms[1 + i] = h->slot.part_ms[i];
     return ISV_OK;
 }
 
@@ -453,7 +435,7 @@ extern "C" int isv_bow_entries(const isv_bow_t *h, int32_t db) {
 
 extern "C" int isv_bow_detect_batch(isv_bow_t *h, int32_t n, const isv_bow_item_t *const *items, isv_bow_result_t *results,
                                     uint32_t *const *word_ids, double *const *word_weights) {
-    InitCall call{h ? h->ctx() : InitCtx{}, "isv_bow_detect_batch"};
+    StageCall call{h ? h->ctx() : StageCtx{}, "isv_bow_detect_batch"};
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_items) return call.fail(ISV_ERR_CAPACITY, "more items than max_items");
     const isv_bow_config_t cfg = h->cfg;
@@ -549,16 +531,15 @@ extern "C" int isv_bow_detect_batch(isv_bow_t *h, int32_t n, const isv_bow_item_
     const BwParams prm{cfg.max_results, cfg.min_gap, cfg.neighbour_score, cfg.loop_score};
     const BwVocabDev V = h->vocab;
     hipStream_t stream = h->stream;
-    hipError_t e_ev = hipSuccess;
     const int rc = call.run(
-        up, clear_end, L.end,
-        [&](char *d, auto &&) {
+        up, {{up.size(), clear_end}}, L.end,
+        [&](char *d, auto &&mark) {
             const BwHdr *dh = (const BwHdr *)(d + o_hd);
             isv_bow_result_t *dr = (isv_bow_result_t *)(d + o_res);
             uint32_t *dvw = (uint32_t *)(d + o_vw);
             double *dvv = (double *)(d + o_vv), *draw = (double *)(d + o_raw);
             hipLaunchKernelGGL(k_bow_transform, dim3(n), dim3(kThreads), sizeof(uint32_t) * P, stream, dh, V, (const uint64_t *)(d + o_ft), dvw, dvv, dr);
-            e_ev = hipEventRecord(h->kev[0], stream);
+            mark();
             if (max_entries > 0) {
                 const dim3 grid(n, (max_entries + kEntriesPerBlock - 1) / kEntriesPerBlock);
                 if (lds_q <= kLdsLimit)
@@ -566,9 +547,9 @@ extern "C" int isv_bow_detect_batch(isv_bow_t *h, int32_t n, const isv_bow_item_
                 else
                     hipLaunchKernelGGL(k_bow_score<false>, grid, dim3(kThreads), 0, stream, dh, dvw, dvv, dr, draw, (int)cfg.min_gap, (int)cfg.max_features);
             }
-            if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[1], stream);
+            mark();
             hipLaunchKernelGGL(k_bow_select, dim3(n), dim3(kLanes), 0, stream, dh, draw, dr, prm);
-            if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[2], stream);
+            mark();
             hipLaunchKernelGGL(k_bow_append, dim3(n), dim3(kThreads), 0, stream, dh, dvw, dvv, dr);
         },
         {{results, o_res, sizeof(isv_bow_result_t) * n}, {word_ids ? vw.data() : nullptr, o_vw, 4 * n_ft},
@@ -585,16 +566,8 @@ extern "C" int isv_bow_detect_batch(isv_bow_t *h, int32_t n, const isv_bow_item_
                 if (nw > 0 && word_ids && word_ids[i]) memcpy(word_ids[i], vw.data() + H.f_off, 4 * (size_t)nw);
                 if (nw > 0 && word_weights && word_weights[i]) memcpy(word_weights[i], vv.data() + H.f_off, 8 * (size_t)nw);
             }
+            return hipSuccess;
         });
     for (BwDb &r : retired) db_free(r);
-    if (rc != ISV_OK) return rc;
-    float ms[4] = {};
-    hipError_t e = e_ev;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], h->slot.ev[0], h->kev[0]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], h->kev[0], h->kev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], h->kev[1], h->kev[2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[3], h->kev[2], h->slot.ev[1]);
-    if (e != hipSuccess) return call.fail(ISV_ERR_DEVICE, hipGetErrorString(e));
-    for (int i = 0; i < 4; i++) h->part_ms[i] = ms[i];
-    return ISV_OK;
+    return rc;
 }

@@ -28,7 +28,7 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_tracker.h"
 #include "isv_detect.h"
 #include "isv_pinhole.h"
@@ -61,9 +61,8 @@ struct isv_det {
     isv_det_config_t cfg;
     isv_trk *trk = nullptr;
     std::string err;
-    InitSlot blk;                 // the call's device block (grow-only)
-    hipEvent_t ev[6] = {};        // before the upload, after it, after k_det_mask, k_det_eig, k_det_select, the download
-    double ms[5] = {};
+    StageSlot slot;               // the call's device block (grow-only), events and times
+    StageCtx ctx() { return StageCtx{trk->device, trk->stream, &slot, &err}; }   // (the device and the stream are the tracker's)
     uint8_t hw[kMaxR + 1];        // the disc of radius min_dist: the half-width per |dy|
     std::vector<char> up;
     std::vector<DetLast> last;    // the last call's items, for the debug read-back
@@ -316,8 +315,7 @@ extern "C" const char *isv_det_last_error(const isv_det_t *h) { return h ? h->er
 extern "C" void isv_det_destroy(isv_det_t *h) {
     if (!h) return;
     (void)hipSetDevice(h->trk->device);
-    init_slot_free(h->blk);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
+    stage_slot_free(h->slot);
     delete h;
 }
 
@@ -334,12 +332,7 @@ extern "C" int isv_det_create(isv_trk_t *trk, const isv_det_config_t *c, isv_det
     disc_table(c->min_dist, h->hw);
     h->named.assign(trk->cfg.max_slots, 0);
     h->stamp.assign(trk->cfg.max_slots, 0);
-    hipError_t e = hipSetDevice(trk->device);
-    for (auto &ev : h->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) {
-        fprintf(stderr, "isv_det_create: %s\n", hipGetErrorString(e));
-        (void)hipGetLastError();
+    if (stage_open_failed("isv_det_create", hipSetDevice(trk->device))) {
         isv_det_destroy(h);
         return ISV_ERR_DEVICE;
     }
@@ -349,13 +342,15 @@ extern "C" int isv_det_create(isv_trk_t *trk, const isv_det_config_t *c, isv_det
 
 extern "C" int isv_det_last_ms(isv_det_t *h, double out_ms[5]) {
     if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
-    memcpy(out_ms, h->ms, sizeof(h->ms));
+    const StageSlot &s = h->slot;      // the marks: after k_det_mask, after k_det_eig
+    out_ms[0] = s.call_ms; out_ms[1] = s.part_ms[1]; out_ms[2] = s.part_ms[0]; out_ms[3] = s.part_ms[2]; out_ms[4] = s.upload_ms + s.download_ms;
     return ISV_OK;
 }
 
 extern "C" int isv_det_detect_batch(isv_det_t *h, int32_t n, const isv_det_item_t *const *items, isv_det_result_t *results, int32_t *const *kept_index,
                                     float *const *new_pts, float *const *new_un_pts) {
-    InitCall call{h ? InitCtx{h->trk->device, h->trk->stream, &h->blk, &h->err} : InitCtx{}, "isv_det_detect_batch"};
+    StageCall call{h ? h->ctx() : StageCtx{}, "isv_det_detect_batch"};
+    call.time_download = true;
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_items) return call.fail(ISV_ERR_CAPACITY, "more items than max_items");
     if (!kept_index || !new_pts || !new_un_pts) return call.fail(ISV_ERR_INVALID_ARG, "null output arrays");
@@ -451,77 +446,54 @@ extern "C" int isv_det_detect_batch(isv_det_t *h, int32_t n, const isv_det_item_
         std::stable_sort(p.begin(), p.end(), [cnt](const DetPoint &a, const DetPoint &b) { return cnt[a.idx] > cnt[b.idx]; });     // G1
         if (!p.empty()) memcpy(up.data() + o_pt + sizeof(DetPoint) * (size_t)dev[k].pt_off, p.data(), sizeof(DetPoint) * p.size());
     }
-    InitSlot &s = h->blk;
-    hipError_t e = hipSuccess;
-    if (L.end > s.cap) {
-        if (s.d) (void)hipFree(s.d);
-        s.d = nullptr; s.cap = 0;
-        if (e = hipMalloc(&s.d, L.end); e != hipSuccess) return call.hip_fail("hipMalloc(&s.d, bytes)", e);
-        s.cap = L.end;
-    }
-    char *d = (char *)s.d;
     hipStream_t stream = trk->stream;
     std::vector<DetCount> cnt(m);
     std::vector<int32_t> dl_kept(n_pt + 1);
     std::vector<float> dl_np(2 * (n_out + 1)), dl_un(2 * (n_out + 1));
-    e = hipEventRecord(h->ev[0], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, up.data(), up.size(), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d + up_end, 0, clear_end - up_end, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_mask, 0xff, mask_bytes, stream);
-    if (e == hipSuccess) e = hipEventRecord(h->ev[1], stream);
-    if (e == hipSuccess) {
-        const DetItem *di = (const DetItem *)(d + o_it);
-        DetCount *dc = (DetCount *)(d + o_cnt);
-        hipLaunchKernelGGL(k_det_mask, dim3(m), dim3(kThreads), 0, stream, di, (const DetPoint *)(d + o_pt), (const uint8_t *)(d + o_hw), d, dc,
-                           (int32_t *)(d + o_kept), cfg.min_dist);
-        e = hipEventRecord(h->ev[2], stream);
-        if (any_new) {
-            const size_t cb = (maxPix + kThreads - 1) / kThreads;
-            hipLaunchKernelGGL(k_det_eig, dim3(m, (maxW + kTW - 1) / kTW, (maxH + kTH - 1) / kTH), dim3(kThreads), 0, stream, di, (const uint8_t *)trk->d_store, d, dc);
-            if (e == hipSuccess) e = hipEventRecord(h->ev[3], stream);
-            hipLaunchKernelGGL(k_det_cand, dim3(m, (unsigned)(cb < (size_t)kCandBlocks ? cb : (size_t)kCandBlocks)), dim3(kThreads), 0, stream, di, d, dc, cfg.quality_level);
-            hipLaunchKernelGGL(k_det_select, dim3(m), dim3(kSelThreads), 0, stream, di, d, dc, trk->cam, (float *)(d + o_np), (float *)(d + o_un), cfg.min_dist);
-        } else if (e == hipSuccess) e = hipEventRecord(h->ev[3], stream);
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->ev[4], stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d + o_cnt, sizeof(DetCount) * m, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && n_pt) e = hipMemcpyAsync(dl_kept.data(), d + o_kept, 4 * n_pt, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && n_out) e = hipMemcpyAsync(dl_np.data(), d + o_np, 8 * n_out, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && n_out) e = hipMemcpyAsync(dl_un.data(), d + o_un, 8 * n_out, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipEventRecord(h->ev[5], stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    float t[5] = {};
-    for (int k = 0; k < 5; k++)
-        if (e == hipSuccess) e = hipEventElapsedTime(&t[k], h->ev[k], h->ev[k + 1]);
-    if (e != hipSuccess) {
-        h->last.clear();
-        return call.fail(ISV_ERR_DEVICE, hipGetErrorString(e));
-    }
-    h->last.assign(n, DetLast{});
-    for (int i = 0; i < n; i++)
-        if (status[i] != ISV_DET_OK) refuse(i);
-    for (int k = 0; k < m; k++) {
-        const int i = who[k];
-        const DetItem &T = dev[k];
-        const DetCount &c = cnt[k];
-        if (c.n_kept) memcpy(kept_index[i], dl_kept.data() + T.pt_off, 4 * (size_t)c.n_kept);
-        if (c.n_new) {
-            memcpy(new_pts[i], dl_np.data() + 2 * (size_t)T.out_off, 8 * (size_t)c.n_new);
-            memcpy(new_un_pts[i], dl_un.data() + 2 * (size_t)T.out_off, 8 * (size_t)c.n_new);
-        }
-        float mv = 0.f;
-        if (c.max_key) {
-            const uint32_t u = (c.max_key >> 31) ? (c.max_key & 0x7fffffffu) : ~c.max_key;
-            memcpy(&mv, &u, 4);
-        }
-        results[i] = isv_det_result_t{ISV_DET_OK, T.np, c.n_kept, c.n_new, (int32_t)c.n_cand, mv};
-        DetLast &l = h->last[i];
-        l.W = T.W; l.H = T.H; l.valid = 1; l.has_eig = T.max_new > 0; l.n_cand = (int32_t)c.n_cand; l.mask_off = T.mask_off; l.eig_off = T.eig_off;
-    }
-    h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call.t_call).count();
-    h->ms[1] = t[2]; h->ms[2] = t[1]; h->ms[3] = t[3]; h->ms[4] = t[0] + t[4];
-    return ISV_OK;
+    const int rc = call.run(
+        up, {{up_end, clear_end}, {o_mask, o_mask + mask_bytes, 0xff}}, L.end,
+        [&](char *d, auto &&mark) {
+            const DetItem *di = (const DetItem *)(d + o_it);
+            DetCount *dc = (DetCount *)(d + o_cnt);
+            hipLaunchKernelGGL(k_det_mask, dim3(m), dim3(kThreads), 0, stream, di, (const DetPoint *)(d + o_pt), (const uint8_t *)(d + o_hw), d, dc,
+                               (int32_t *)(d + o_kept), cfg.min_dist);
+            mark();
+            if (any_new) {
+                const size_t cb = (maxPix + kThreads - 1) / kThreads;
+                hipLaunchKernelGGL(k_det_eig, dim3(m, (maxW + kTW - 1) / kTW, (maxH + kTH - 1) / kTH), dim3(kThreads), 0, stream, di, (const uint8_t *)trk->d_store, d, dc);
+                mark();
+                hipLaunchKernelGGL(k_det_cand, dim3(m, (unsigned)(cb < (size_t)kCandBlocks ? cb : (size_t)kCandBlocks)), dim3(kThreads), 0, stream, di, d, dc, cfg.quality_level);
+                hipLaunchKernelGGL(k_det_select, dim3(m), dim3(kSelThreads), 0, stream, di, d, dc, trk->cam, (float *)(d + o_np), (float *)(d + o_un), cfg.min_dist);
+            } else mark();
+        },
+        {{cnt.data(), o_cnt, sizeof(DetCount) * m}, {n_pt ? dl_kept.data() : nullptr, o_kept, 4 * n_pt}, {n_out ? dl_np.data() : nullptr, o_np, 8 * n_out},
+         {n_out ? dl_un.data() : nullptr, o_un, 8 * n_out}},
+        [&] {
+            h->last.assign(n, DetLast{});
+            for (int i = 0; i < n; i++)
+                if (status[i] != ISV_DET_OK) refuse(i);
+            for (int k = 0; k < m; k++) {
+                const int i = who[k];
+                const DetItem &T = dev[k];
+                const DetCount &c = cnt[k];
+                if (c.n_kept) memcpy(kept_index[i], dl_kept.data() + T.pt_off, 4 * (size_t)c.n_kept);
+                if (c.n_new) {
+                    memcpy(new_pts[i], dl_np.data() + 2 * (size_t)T.out_off, 8 * (size_t)c.n_new);
+                    memcpy(new_un_pts[i], dl_un.data() + 2 * (size_t)T.out_off, 8 * (size_t)c.n_new);
+                }
+                float mv = 0.f;
+                if (c.max_key) {
+                    const uint32_t u = (c.max_key >> 31) ? (c.max_key & 0x7fffffffu) : ~c.max_key;
+                    memcpy(&mv, &u, 4);
+                }
+                results[i] = isv_det_result_t{ISV_DET_OK, T.np, c.n_kept, c.n_new, (int32_t)c.n_cand, mv};
+                DetLast &l = h->last[i];
+                l.W = T.W; l.H = T.H; l.valid = 1; l.has_eig = T.max_new > 0; l.n_cand = (int32_t)c.n_cand; l.mask_off = T.mask_off; l.eig_off = T.eig_off;
+            }
+            return hipSuccess;
+        });
+    if (rc != ISV_OK) h->last.clear();
+    return rc;
 }
 
 extern "C" int isv_internal_det_read_plane(isv_det_t *h, int32_t item, int32_t which, void *out, int32_t *width, int32_t *height, int32_t *n_candidates) {
@@ -534,7 +506,7 @@ extern "C" int isv_internal_det_read_plane(isv_det_t *h, int32_t item, int32_t w
     if (!out) return ISV_OK;
     HIPCHK(h, hipSetDevice(h->trk->device));
     const size_t px = (size_t)l.W * l.H;
-    HIPCHK(h, hipMemcpyAsync(out, (char *)h->blk.d + (which == 0 ? l.eig_off : l.mask_off), which == 0 ? 4 * px : px, hipMemcpyDeviceToHost, h->trk->stream));
+    HIPCHK(h, hipMemcpyAsync(out, (char *)h->slot.d + (which == 0 ? l.eig_off : l.mask_off), which == 0 ? 4 * px : px, hipMemcpyDeviceToHost, h->trk->stream));
     HIPCHK(h, hipStreamSynchronize(h->trk->stream));
     return ISV_OK;
 }

@@ -16,7 +16,7 @@
 #include <float.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_device_math.h"
 #include "isv_initial.h"
 
@@ -503,7 +503,7 @@ int check_problem(const isv_align_problem_t *p, ProbHdr *hd) {
 extern "C" int isv_internal_align_last_ms(isv_backend_t *h, double out_ms[2]) { return init_last_ms(h, ISV_INIT_ALIGN, out_ms); }
 
 extern "C" int isv_internal_visual_imu_align_batch(isv_backend_t *h, int32_t n, const isv_align_problem_t *const *problems, isv_align_result_t *results) {
-    InitCall call{init_ctx(h, ISV_INIT_ALIGN), "isv_internal_visual_imu_align_batch"};
+    StageCall call{init_ctx(h, ISV_INIT_ALIGN), "isv_internal_visual_imu_align_batch"};
     if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<ProbHdr> hd(n);
     size_t n_frames = 0, n_imu = 0;
@@ -538,10 +538,10 @@ extern "C" int isv_internal_visual_imu_align_batch(isv_backend_t *h, int32_t n, 
     const size_t lds = lds_bytes(nf_max);
     HIPCHK(h, isv_raise_dynamic_lds((const void *)k_visual_imu_align, h->device, lds));
     return call.run(
-        up, L.end, L.end,
+        up, {{up.size(), L.end}}, L.end,
         [&](char *d, auto &&) {
             hipLaunchKernelGGL(k_visual_imu_align, dim3(n), dim3(kLanes), lds, h->stream, (const ProbHdr *)(d + o_hd), (const isv_align_frame_t *)(d + o_fr),
                                (const double *)(d + o_imu), (isv_align_result_t *)(d + o_res), nf_max);
         },
-        {{results, o_res, sizeof(isv_align_result_t) * n}}, [] {});
+        {{results, o_res, sizeof(isv_align_result_t) * n}}, [] { return hipSuccess; });
 }

@@ -1,7 +1,7 @@
 // isv_keyframe.hip -- batched keyframe extraction: cv::FAST, the BRIEF descriptors of the corners and of the window points and
 // liftProjective of every corner, for many 8-bit images in one call (include/isvins_keyframe.h has the contract, the reference
 // lines, the restated OpenCV pieces and the quirks K1..K6; the serial CPU restatement is tests/native/isv_kf_oracle.c).
-// One packed upload, four kernels, one download (isv_init_launch.h).  Integers everywhere except the lift.
+// One packed upload, four kernels, one download (isv_stage_launch.h).  Integers everywhere except the lift.
 //
 // k_kf_blur: one workgroup per 64 x 16 tile.  The tile and a 4-pixel halo go into LDS with BORDER_REFLECT_101 applied on the way
 // in, so that neither pass sees a border; the row pass fills a 16-bit LDS plane of (16 + 8) x 64, the column pass reads it.
@@ -20,7 +20,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_keyframe.h"
 #include "isv_pinhole.h"
 
@@ -42,20 +42,14 @@ struct KfLast { int32_t status, W, H; uint64_t img_off; };
 
 }  // namespace
 
-struct isv_kf {
+struct isv_kf : StageHandle {
     isv_kf_config_t cfg;
     PinholeCam cam;
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    InitSlot slot;                // the call's device block (grow-only), events and times
-    hipEvent_t kev[4] = {};       // before the upload, and between the four kernels
-    double part_ms[6] = {};       // the four kernels, the upload, the host's packing
+    double pack_ms = 0;           // the host's packing of the last successful call
     int8_t *d_pattern = nullptr;  // [4][256]: x1, y1, x2, y2
     std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
     std::vector<KfLast> last;     // the last successful call's items, for the debug read-back
     size_t last_blur = 0, last_smap = 0;
-    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
 };
 
 // BORDER_REFLECT_101 (cv::borderInterpolate): always inside [0, len)
@@ -322,11 +316,8 @@ extern "C" const char *isv_kf_last_error(const isv_kf_t *h) { return h ? h->err.
 
 extern "C" void isv_kf_destroy(isv_kf_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    init_slot_free(h->slot);
+    h->close();
     if (h->d_pattern) (void)hipFree(h->d_pattern);
-    for (auto &e : h->kev) if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -345,22 +336,14 @@ extern "C" int isv_kf_create(const isv_kf_config_t *c, isv_kf_t **out) {
     isv_kf *h = new isv_kf();
     h->cfg = *c;
     h->cam = pinhole_make(c->fx, c->fy, c->cx, c->cy, c->k1, c->k2, c->p1, c->p2);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e == hipSuccess && ndev <= 0) e = hipErrorNoDevice;
-    if (e == hipSuccess) e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (auto &ev : h->kev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
+    hipError_t e = h->open();
     if (e == hipSuccess) e = hipMalloc(&h->d_pattern, 4 * ISV_KF_PATTERN_BITS);
     if (e == hipSuccess) {
         int8_t pat[4 * ISV_KF_PATTERN_BITS];
         memcpy(pat, c->x1, 256); memcpy(pat + 256, c->y1, 256); memcpy(pat + 512, c->x2, 256); memcpy(pat + 768, c->y2, 256);
         e = hipMemcpy(h->d_pattern, pat, sizeof(pat), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
-        fprintf(stderr, "isv_kf_create: %s\n", hipGetErrorString(e));
-        (void)hipGetLastError();
+    if (stage_open_failed("isv_kf_create", e)) {
         isv_kf_destroy(h);
         return ISV_ERR_DEVICE;
     }
@@ -371,13 +354,14 @@ extern "C" int isv_kf_create(const isv_kf_config_t *c, isv_kf_t **out) {
 extern "C" int isv_kf_last_ms(isv_kf_t *h, double out_ms[7]) {
     if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
     out_ms[0] = h->slot.call_ms;
-    for (int i = 0; i < 6; i++) out_ms[1 + i] = h->part_ms[i];
+    for (int i = 0; i < 4; i++) out_ms[1 + i] = h->slot.part_ms[i];   // blur, FAST, select, BRIEF
+    out_ms[5] = h->slot.upload_ms; out_ms[6] = h->pack_ms;
     return ISV_OK;
 }
 
 extern "C" int isv_kf_extract_batch(isv_kf_t *h, int32_t n, const isv_kf_item_t *const *items, isv_kf_result_t *results, uint64_t *const *brief,
                                     float *const *keypoints_uv, float *const *keypoints_norm, uint8_t *const *score, uint64_t *const *window_brief) {
-    InitCall call{h ? h->ctx() : InitCtx{}, "isv_kf_extract_batch"};
+    StageCall call{h ? h->ctx() : StageCtx{}, "isv_kf_extract_batch"};
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_items) return call.fail(ISV_ERR_CAPACITY, "more items than max_items");
     if (!brief || !keypoints_uv || !keypoints_norm || !score || !window_brief) return call.fail(ISV_ERR_INVALID_ARG, "null output arrays");
@@ -430,23 +414,22 @@ extern "C" int isv_kf_extract_batch(isv_kf_t *h, int32_t n, const isv_kf_item_t 
     }
     const double pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pack).count();
     hipStream_t stream = h->stream;
-    hipError_t e_ev = hipEventRecord(h->kev[0], stream), e_post = hipSuccess;
     std::vector<char> dl;
     const int rc = call.run(
-        up, clear_end, L.end,
-        [&](char *d, auto &&) {
+        up, {{up.size(), clear_end}}, L.end,
+        [&](char *d, auto &&mark) {
             const KfHdr *dh = (const KfHdr *)(d + o_hd);
             isv_kf_result_t *dr = (isv_kf_result_t *)(d + o_res);
             if (maxW > 0 && maxH > 0) {
                 const dim3 grid((maxW + kTW - 1) / kTW, (maxH + kTH - 1) / kTH, n);
                 hipLaunchKernelGGL(k_kf_blur, grid, dim3(kThreads), 0, stream, dh, (const uint8_t *)(d + o_img), (uint8_t *)(d + o_blur));
-                if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[1], stream);
+                mark();
                 hipLaunchKernelGGL(k_kf_fast, grid, dim3(kThreads), 0, stream, dh, (const uint8_t *)(d + o_img), (uint8_t *)(d + o_smap), (int)cfg.fast_threshold);
-            } else if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[1], stream);
-            if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[2], stream);
+            } else mark();
+            mark();
             hipLaunchKernelGGL(k_kf_select, dim3(n), dim3(kSelThreads), sizeof(int) * (size_t)(maxH > 0 ? maxH : 1), stream, dh, (const uint8_t *)(d + o_smap),
                                (uint32_t *)(d + o_kxy), (uint8_t *)(d + o_ksc), dr, (int)cfg.max_keypoints);
-            if (e_ev == hipSuccess) e_ev = hipEventRecord(h->kev[3], stream);
+            mark();
             hipLaunchKernelGGL(k_kf_brief, dim3(kBriefBlocks, n), dim3(kBriefWaves * kLanes), 0, stream, dh, dr, (const uint8_t *)(d + o_blur), h->d_pattern,
                                (const float *)(d + o_pt), (const uint32_t *)(d + o_kxy), (const uint8_t *)(d + o_ksc), h->cam, (uint64_t *)(d + o_br),
                                (float *)(d + o_uv), (float *)(d + o_nm), (uint8_t *)(d + o_sc), (uint64_t *)(d + o_wb));
@@ -471,7 +454,7 @@ extern "C" int isv_kf_extract_batch(isv_kf_t *h, int32_t n, const isv_kf_item_t 
             }
             if (e == hipSuccess && n_pt) e = hipMemcpyAsync(dl.data() + b_wb, d + o_wb, 32 * n_pt, hipMemcpyDeviceToHost, stream);
             if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) { e_post = e; return; }
+            if (e != hipSuccess) return e;
             size_t at = 0;
             for (int i = 0; i < n; i++) {
                 if (hd[i].status != ISV_KF_OK || results[i].status != ISV_KF_OK) continue;
@@ -485,18 +468,10 @@ extern "C" int isv_kf_extract_batch(isv_kf_t *h, int32_t n, const isv_kf_item_t 
                 if (np) memcpy(window_brief[i], dl.data() + b_wb + 32 * (size_t)hd[i].pt_off, 32 * np);
                 at += nk;
             }
+            return hipSuccess;
         });
     if (rc != ISV_OK) { h->last.clear(); return rc; }
-    float ms[5] = {};
-    hipError_t e = e_post != hipSuccess ? e_post : e_ev;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[0], h->slot.ev[0], h->kev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[1], h->kev[1], h->kev[2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[2], h->kev[2], h->kev[3]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[3], h->kev[3], h->slot.ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms[4], h->kev[0], h->slot.ev[0]);
-    if (e != hipSuccess) { h->last.clear(); return call.fail(ISV_ERR_DEVICE, hipGetErrorString(e)); }
-    for (int i = 0; i < 5; i++) h->part_ms[i] = ms[i];
-    h->part_ms[5] = pack_ms;
+    h->pack_ms = pack_ms;
     h->last.resize(n);
     for (int i = 0; i < n; i++) h->last[i] = KfLast{hd[i].status, hd[i].W, hd[i].H, hd[i].img_off};
     h->last_blur = o_blur; h->last_smap = o_smap;

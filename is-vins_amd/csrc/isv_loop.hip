@@ -1,7 +1,7 @@
 // isv_loop.hip -- batched loop-closure verification, KeyFrame::findConnection for many keyframe pairs in one call
 // (include/isvins_loop.h has the contract, the reference lines, the restated OpenCV pieces, the quirks L1..L6 and the
 // deviations; the serial pieces are isv_loop_common.h / isv_pnp.h / isv_init_common.h, shared with the CPU restatement
-// tests/native/isv_loop_oracle.c).  One packed upload, two kernels, one download (isv_init_launch.h).
+// tests/native/isv_loop_oracle.c).  One packed upload, two kernels, one download (isv_stage_launch.h).
 //
 // k_loop_match: one workgroup of four wavefronts per pair, integers only.  The old keyframe's descriptors pass through an LDS
 // tile of kTile descriptors, stored as two planes of 16 bytes per descriptor so that consecutive lanes read consecutive
@@ -22,16 +22,11 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_loop_common.h"
 
-struct isv_loop {
+struct isv_loop : StageHandle {
     isv_loop_config_t cfg;
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    InitSlot slot;                // the call's device block (grow-only), events and times
-    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
 };
 
 namespace {
@@ -293,9 +288,7 @@ extern "C" const char *isv_loop_last_error(const isv_loop_t *h) { return h ? h->
 
 extern "C" void isv_loop_destroy(isv_loop_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    init_slot_free(h->slot);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
@@ -310,14 +303,7 @@ extern "C" int isv_loop_create(const isv_loop_config_t *c, isv_loop_t **out) {
         return ISV_ERR_INVALID_ARG;
     isv_loop *h = new isv_loop();
     h->cfg = *c;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e == hipSuccess && ndev <= 0) e = hipErrorNoDevice;
-    if (e == hipSuccess) e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        fprintf(stderr, "isv_loop_create: %s\n", hipGetErrorString(e));
-        (void)hipGetLastError();
+    if (stage_open_failed("isv_loop_create", h->open())) {
         isv_loop_destroy(h);
         return ISV_ERR_DEVICE;
     }
@@ -343,7 +329,7 @@ extern "C" int isv_loop_apply(const isv_loop_result_t *r, isv_pg_keyframe_t *cur
 
 extern "C" int isv_loop_verify_batch(isv_loop_t *h, int32_t n, const isv_loop_pair_t *const *pairs, isv_loop_result_t *results,
                                      int32_t *const *match_index, int32_t *const *match_dist, int32_t *const *inlier) {
-    InitCall call{h ? h->ctx() : InitCtx{}, "isv_loop_verify_batch"};
+    StageCall call{h ? h->ctx() : StageCtx{}, "isv_loop_verify_batch"};
     if (const int rc = call.enter(n, pairs, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_pairs) return call.fail(ISV_ERR_CAPACITY, "more pairs than max_pairs");
     std::vector<LpHdr> hd(n);
@@ -387,13 +373,13 @@ extern "C" int isv_loop_verify_batch(isv_loop_t *h, int32_t n, const isv_loop_pa
     const isv_loop_config_t cfg = h->cfg;
     hipStream_t stream = h->stream;
     return call.run(
-        up, o_key, L.end,
-        [&](char *d, auto &&between) {
+        up, {{up.size(), o_key}}, L.end,
+        [&](char *d, auto &&mark) {
             hipLaunchKernelGGL(k_loop_match, dim3(n), dim3(kMatchThreads), 0, stream, (const LpHdr *)(d + o_hd), (const uint64_t *)(d + o_wb),
                                (const float *)(d + o_x), (const uint64_t *)(d + o_kb), (const float *)(d + o_kp), (uint32_t *)(d + o_key),
                                (int32_t *)(d + o_mi), (int32_t *)(d + o_md), (lp_match_t *)(d + o_list), (isv_loop_result_t *)(d + o_res),
                                (int)cfg.match_max_dist, (int)cfg.match_accept_dist);
-            between();
+            mark();
             hipLaunchKernelGGL(k_loop_pnp, dim3(n), dim3(kLanes), 0, stream, cfg, (const LpHdr *)(d + o_hd), (const lp_match_t *)(d + o_list),
                                (isv_loop_result_t *)(d + o_res), (int32_t *)(d + o_in), (double *)(d + o_pp), (double *)(d + o_term));
         },
@@ -407,5 +393,6 @@ extern "C" int isv_loop_verify_batch(isv_loop_t *h, int32_t n, const isv_loop_pa
                 if (match_dist && match_dist[i]) memcpy(match_dist[i], md.data() + H.pt_off, 4 * (size_t)H.np);
                 if (inlier && inlier[i]) memcpy(inlier[i], in.data() + H.pt_off, 4 * (size_t)H.np);
             }
+            return hipSuccess;
         });
 }

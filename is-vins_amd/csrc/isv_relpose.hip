@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_relpose.h"
 #include "isv_init_common.h"
 
@@ -230,7 +230,7 @@ extern "C" int isv_internal_relpose_last_ms(isv_backend_t *h, double out_ms[2]) 
 
 extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv_sfm_problem_t *const *problems, isv_relpose_result_t *results,
                                           int32_t *const *masks) {
-    InitCall call{init_ctx(h, ISV_INIT_RELPOSE), "isv_internal_relpose_batch"};
+    StageCall call{init_ctx(h, ISV_INIT_RELPOSE), "isv_internal_relpose_batch"};
     if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<RpHdr> hd(n);
     size_t n_tr = 0, n_obs = 0, n_fr = 0;
@@ -263,7 +263,7 @@ extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv
     }
     std::vector<int32_t> mk(n_tr + 1);
     return call.run(
-        up, o_mask, L.end,
+        up, {{up.size(), o_mask}}, L.end,
         [&](char *d, auto &&) {
             hipLaunchKernelGGL(k_relpose, dim3(n), dim3(kLanes), 0, h->stream, (const RpHdr *)(d + o_hd), (const isv_sfm_track_t *)(d + o_tr),
                                (const double *)(d + o_obs), (const double *)(d + o_dv), (const double *)(d + o_sdt),
@@ -277,5 +277,6 @@ extern "C" int isv_internal_relpose_batch(isv_backend_t *h, int32_t n, const isv
                     const RpHdr &H = hd[i];
                     if (H.status == ISV_RELPOSE_OK) memcpy(masks[i], mk.data() + H.trk_off, 4 * (size_t)H.ntr);   // (a refused input's n_tracks is not trusted)
                 }
+            return hipSuccess;
         });
 }

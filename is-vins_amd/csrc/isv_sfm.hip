@@ -19,7 +19,7 @@
 #include <string.h>
 #include <unordered_map>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_sfm.h"
 #include "isv_init_common.h"
 #include "isv_pnp.h"
@@ -817,7 +817,7 @@ int isv_sfm_check_problem(const isv_sfm_problem_t *p, bool with_l) {
 extern "C" int isv_internal_sfm_last_ms(isv_backend_t *h, double out_ms[2]) { return init_last_ms(h, ISV_INIT_SFM, out_ms); }
 
 extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm_problem_t *const *problems, isv_sfm_result_t *results) {
-    InitCall call{init_ctx(h, ISV_INIT_SFM), "isv_internal_sfm_batch"};
+    StageCall call{init_ctx(h, ISV_INIT_SFM), "isv_internal_sfm_batch"};
     if (const int rc = call.enter(n, problems, results); rc != ISV_OK || n == 0) return rc;
     std::vector<SfmHdr> hd(n);
     size_t n_tr = 0, n_obs = 0, n_poff = 0, n_pts = 0, n_fr = 0;
@@ -875,7 +875,7 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
     std::vector<double> pos(3 * (n_tr + 1));
     std::vector<int32_t> st(n_tr + 1);
     return call.run(
-        up, o_scr, L.end,
+        up, {{up.size(), o_scr}}, L.end,
         [&](char *d, auto &&) {
             hipLaunchKernelGGL(k_sfm, dim3(n), dim3(kLanes), lds, h->stream, (const SfmHdr *)(d + o_hd), (const isv_sfm_track_t *)(d + o_tr),
                                (const double *)(d + o_obs), (const int32_t *)(d + o_poff), (const int32_t *)(d + o_ptrk), (const double *)(d + o_uv),
@@ -891,5 +891,6 @@ extern "C" int isv_internal_sfm_batch(isv_backend_t *h, int32_t n, const isv_sfm
                 memcpy(problems[i]->position, pos.data() + 3 * (size_t)H.trk_off, 24 * (size_t)H.ntr);
                 memcpy(problems[i]->state, st.data() + H.trk_off, 4 * (size_t)H.ntr);
             }
+            return hipSuccess;
         });
 }

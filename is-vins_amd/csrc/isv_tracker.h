@@ -18,7 +18,7 @@ int isv_internal_trk_read_level(isv_trk_t *h, int32_t slot, int32_t which, int32
 #endif
 
 #ifdef __HIPCC__
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_pinhole.h"
 
 constexpr int kTrkLevels = ISV_TRK_MAX_LEVEL + 1;
@@ -31,15 +31,10 @@ struct TrkShape {                 // a pyramid's levels: sizes and packed offset
 
 struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0; };      // par: which of the slot's two buffers is resident
 
-struct isv_trk {
+struct isv_trk : StageHandle {
     isv_trk_config_t cfg;
     PinholeCam cam;
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    InitSlot slot;                // the call's device block (grow-only), events and times
-    hipEvent_t kev = nullptr;     // before the upload
-    double upload_ms = 0, pack_ms = 0;
+    double pack_ms = 0;           // the host's packing of the last successful call
     uint8_t *d_store = nullptr;   // [max_slots][2][slot_bytes]: the slots' pyramids
     size_t slot_bytes = 0;        // a pyramid of max_width x max_height, rounded up to 256
     std::vector<TrkSlot> slots;
@@ -47,7 +42,6 @@ struct isv_trk {
     std::vector<int64_t> stamp;
     int64_t serial = 0;
     std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
-    InitCtx ctx() { return InitCtx{device, stream, &slot, &err}; }
     // the store offset of a slot's buffer; level 0 of a pyramid is at its start
     size_t store_off(int slot_i, int buf) const { return ((size_t)slot_i * 2 + buf) * slot_bytes; }
 };

@@ -1,7 +1,7 @@
 // isv_tracker.hip -- batched feature tracking: cv::calcOpticalFlowPyrLK(21 x 21, 3 levels down), inBorder and liftProjective of every
 // tracked point for many sequences in one call (include/isvins_tracker.h has the contract, the reference lines, the restated OpenCV
 // pieces, the quirks T1..T4 and the deviations D1, D2; the serial CPU restatement is tests/native/isv_trk_oracle.c).
-// One packed upload, the pyramid kernels, one tracking kernel, one download (isv_init_launch.h).  Integers everywhere except the
+// One packed upload, the pyramid kernels, one tracking kernel, one download (isv_stage_launch.h).  Integers everywhere except the
 // 2 x 2 solve of a step (float32, one fixed order) and the lift (isv_pinhole.h).
 //
 // A slot owns two pyramid buffers in the handle's store, allocated at creation: the resident one (the last cur image's) and the one
@@ -25,7 +25,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <vector>
-#include "isv_init_launch.h"
+#include "isv_stage_launch.h"
 #include "isv_tracker.h"
 #include "isv_pinhole.h"
 
@@ -322,11 +322,8 @@ extern "C" const char *isv_trk_last_error(const isv_trk_t *h) { return h ? h->er
 
 extern "C" void isv_trk_destroy(isv_trk_t *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    init_slot_free(h->slot);
+    h->close();
     if (h->d_store) (void)hipFree(h->d_store);
-    if (h->kev) (void)hipEventDestroy(h->kev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -347,16 +344,9 @@ extern "C" int isv_trk_create(const isv_trk_config_t *c, isv_trk_t **out) {
     h->slots.resize(c->max_slots);
     h->named.assign(c->max_slots, 0);
     h->stamp.assign(c->max_slots, 0);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e == hipSuccess && ndev <= 0) e = hipErrorNoDevice;
-    if (e == hipSuccess) e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->kev);
+    hipError_t e = h->open();
     if (e == hipSuccess) e = hipMalloc(&h->d_store, h->slot_bytes * 2 * (size_t)c->max_slots);
-    if (e != hipSuccess) {
-        fprintf(stderr, "isv_trk_create: %s\n", hipGetErrorString(e));
-        (void)hipGetLastError();
+    if (stage_open_failed("isv_trk_create", e)) {
         isv_trk_destroy(h);
         return ISV_ERR_DEVICE;
     }
@@ -367,7 +357,7 @@ extern "C" int isv_trk_create(const isv_trk_config_t *c, isv_trk_t **out) {
 extern "C" int isv_trk_last_ms(isv_trk_t *h, double out_ms[5]) {
     if (!h || !out_ms) return ISV_ERR_INVALID_ARG;
     out_ms[0] = h->slot.call_ms; out_ms[1] = h->slot.part_ms[0]; out_ms[2] = h->slot.part_ms[1];
-    out_ms[3] = h->upload_ms; out_ms[4] = h->pack_ms;
+    out_ms[3] = h->slot.upload_ms; out_ms[4] = h->pack_ms;
     return ISV_OK;
 }
 
@@ -379,7 +369,7 @@ extern "C" int isv_trk_slot_reset(isv_trk_t *h, int32_t slot) {
 
 extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results, float *const *cur_pts,
                                    uint8_t *const *flags, float *const *err, float *const *cur_un_pts) {
-    InitCall call{h ? h->ctx() : InitCtx{}, "isv_trk_track_batch"};
+    StageCall call{h ? h->ctx() : StageCtx{}, "isv_trk_track_batch"};
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_items) return call.fail(ISV_ERR_CAPACITY, "more items than max_items");
     if (!cur_pts || !flags || !err || !cur_un_pts) return call.fail(ISV_ERR_INVALID_ARG, "null output arrays");
@@ -460,17 +450,16 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
     }
     const double pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pack).count();
     hipStream_t stream = h->stream;
-    hipError_t e_ev = hipEventRecord(h->kev, stream);
     std::vector<char> dl(21 * n_pt + 32);
     const size_t b_cp = 0, b_un = 8 * n_pt, b_er = 16 * n_pt, b_fl = 20 * n_pt;
     const int rc = call.run(
-        up, clear_end, L.end,
-        [&](char *d, auto &&between) {
+        up, {{up.size(), clear_end}}, L.end,
+        [&](char *d, auto &&mark) {
             const TrkJob *dj = (const TrkJob *)(d + o_job);
             hipLaunchKernelGGL(k_trk_level0, dim3(nj, kCopyBlocks), dim3(kCopyThreads), 0, stream, dj, (const uint8_t *)(d + o_img), h->d_store);
             for (int l = 1; l < maxLev; l++)
                 hipLaunchKernelGGL(k_trk_pyrdown, dim3(nj, (maxLW[l] + kPW - 1) / kPW, (maxLH[l] + kPH - 1) / kPH), dim3(kPThreads), 0, stream, dj, h->d_store, l);
-            between();
+            mark();
             if (maxNp > 0)
                 hipLaunchKernelGGL(k_trk_track, dim3(maxNp, m), dim3(kLanes), 0, stream, (const TrkItem *)(d + o_it), (const float *)(d + o_pt),
                                    (const uint8_t *)h->d_store, h->cam, (float *)(d + o_cp), (float *)(d + o_un), (float *)(d + o_er), (uint8_t *)(d + o_fl));
@@ -494,16 +483,13 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
                 results[i] = isv_trk_result_t{ISV_TRK_OK, (int32_t)np, kept, dev[k].s.nlev};
                 h->slots[items[i]->slot] = TrkSlot{items[i]->width, items[i]->height, (int32_t)((dev[k].cur_off - h->store_off(items[i]->slot, 0)) / h->slot_bytes), 1};
             }
+            return hipSuccess;
         });
     if (rc != ISV_OK) {                            // what the kernels left in the buffers is unknown
         for (int k = 0; k < m; k++) h->slots[items[who[k]]->slot] = TrkSlot{};
         return rc;
     }
-    float ms = 0.f;
-    hipError_t e = e_ev;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->kev, h->slot.ev[0]);
-    if (e != hipSuccess) return call.fail(ISV_ERR_DEVICE, hipGetErrorString(e));
-    h->upload_ms = ms; h->pack_ms = pack_ms;
+    h->pack_ms = pack_ms;
     return ISV_OK;
 }
 

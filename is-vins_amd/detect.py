@@ -7,8 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import backend
-from .tracker import FILL
+from . import _stage
+from ._stage import filled, untouched
 
 ISV_DET_OK, ISV_DET_CAPACITY, ISV_DET_INPUT = range(3)
 BLOCK_SIZE, APERTURE, USE_HARRIS = 3, 3, 0
@@ -69,23 +69,8 @@ class DetArrays:
         self.kept_index, self.new_pts, self.new_un_pts = kept_index, new_pts, new_un_pts
 
 
-def filled(rows, cols, dtype):
-    """an output array pre-filled with FILL bytes"""
-    return np.full((max(rows, 1), cols * 4), FILL, dtype=np.uint8).view(dtype)
-
-
-def untouched(a, used):
-    """nothing is written past `used` rows"""
-    return bool((a.view(np.uint8).reshape(len(a), -1)[used:] == FILL).all())
-
-
-_bound = False
-
-
+@_stage.bind_once("det")
 def _bind(lib):
-    global _bound
-    if _bound:
-        return
     vp = C.c_void_p
     lib.isv_det_create.argtypes = [vp, C.POINTER(isv_det_config_t), C.POINTER(vp)]
     lib.isv_det_destroy.argtypes = [vp]; lib.isv_det_destroy.restype = None
@@ -94,33 +79,17 @@ def _bind(lib):
                                          C.POINTER(_f32p), C.POINTER(_f32p)]
     lib.isv_det_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.isv_internal_det_read_plane.argtypes = [vp, C.c_int32, C.c_int32, vp, _i32p, _i32p, _i32p]
-    _bound = True
 
 
-class Detector:
+class Detector(_stage.StageHandle):
     """setMask + goodFeaturesToTrack on the MI355X, on the slots of a tracker.Tracker: many sequences per call.  Close it before
     its tracker."""
+    PREFIX, N_MS = "isv_det", 5
 
     def __init__(self, tracker, max_items=None, **kw):
-        self.lib = backend.load_library()
-        _bind(self.lib)
         self.tracker = tracker                     # kept alive: the detector uses its slots, stream and camera
         self.cfg = make_config(tracker.cfg.max_items if max_items is None else max_items, **kw)
-        self.h = C.c_void_p()
-        rc = self.lib.isv_det_create(tracker.h, C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise backend.BackendError(f"isv_det_create: {backend.STATUS.get(rc, rc)}")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.isv_det_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(_bind, tracker.h, C.byref(self.cfg))
 
     def detect_batch(self, items):
         """items: DetItem list -> (isv_det_result_t list, DetArrays list).  The arrays are pre-filled with FILL bytes; what lies
@@ -134,9 +103,7 @@ class Detector:
         un = [filled(min(max(it.c.max_new, 0), cap), 2, np.float32) for it in items]
         arr = lambda t, xs: (t * max(n, 1))(*[a.ctypes.data_as(t) for a in xs])
         rc = self.lib.isv_det_detect_batch(self.h, n, ptrs, res, arr(_i32p, ki), arr(_f32p, nw), arr(_f32p, un))
-        if rc != 0:
-            msg = self.lib.isv_det_last_error(self.h)
-            raise backend.BackendError(f"isv_det_detect_batch: {backend.STATUS.get(rc, rc)} {msg.decode() if msg else ''}")
+        self._check(rc, "isv_det_detect_batch", with_last_error=True)
         out = list(res)[:n]
         arrays = []
         for i, r in enumerate(out):
@@ -150,19 +117,11 @@ class Detector:
         """a plane of item `item` of the last call (debug entry, csrc/isv_detect.h): which = 0 the response (float32), 1 the mask
         (uint8) -> (plane [height][width], n_candidates)"""
         w, h, nc = C.c_int32(), C.c_int32(), C.c_int32()
-        rc = self.lib.isv_internal_det_read_plane(self.h, item, which, None, C.byref(w), C.byref(h), C.byref(nc))
-        if rc != 0:
-            raise backend.BackendError(f"isv_internal_det_read_plane: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_internal_det_read_plane(self.h, item, which, None, C.byref(w), C.byref(h), C.byref(nc)), "isv_internal_det_read_plane")
         out = np.zeros((h.value, w.value), np.float32 if which == 0 else np.uint8)
-        rc = self.lib.isv_internal_det_read_plane(self.h, item, which, out.ctypes.data_as(C.c_void_p), None, None, None)
-        if rc != 0:
-            raise backend.BackendError(f"isv_internal_det_read_plane: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_internal_det_read_plane(self.h, item, which, out.ctypes.data_as(C.c_void_p), None, None, None), "isv_internal_det_read_plane")
         return out, nc.value
 
     def last_ms(self):
         """(whole call, k_det_eig, k_det_mask, k_det_cand + k_det_select, upload + download) milliseconds of the last successful call"""
-        ms = (C.c_double * 5)()
-        rc = self.lib.isv_det_last_ms(self.h, ms)
-        if rc != 0:
-            raise backend.BackendError(f"isv_det_last_ms: {backend.STATUS.get(rc, rc)}")
-        return tuple(ms)
+        return super().last_ms()

@@ -10,7 +10,8 @@ import os
 
 import numpy as np
 
-from . import backend, synth
+from . import _stage, synth
+from ._stage import filled, untouched
 
 ISV_KF_OK, ISV_KF_CAPACITY, ISV_KF_INPUT = range(3)
 PATTERN_BITS, PATTERN_RADIUS = 256, 24
@@ -129,14 +130,8 @@ class KfArrays:
         self.brief, self.keypoints_uv, self.keypoints_norm, self.score, self.window_brief = brief, keypoints_uv, keypoints_norm, score, window_brief
 
 
-_bound = False
-FILL = 0xA5                                # the pattern the output arrays are pre-filled with
-
-
+@_stage.bind_once("kf")
 def _bind(lib):
-    global _bound
-    if _bound:
-        return
     vp = C.c_void_p
     lib.isv_kf_create.argtypes = [C.POINTER(isv_kf_config_t), C.POINTER(vp)]
     lib.isv_kf_destroy.argtypes = [vp]; lib.isv_kf_destroy.restype = None
@@ -145,7 +140,6 @@ def _bind(lib):
                                          C.POINTER(_f32p), C.POINTER(_f32p), C.POINTER(_u8p), C.POINTER(_u64p)]
     lib.isv_kf_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.isv_internal_kf_read_back.argtypes = [vp, C.c_int32, _u8p, _u8p]
-    _bound = True
 
 
 def keypoint_capacity(cfg, item):
@@ -154,28 +148,13 @@ def keypoint_capacity(cfg, item):
     return min(cfg.max_keypoints, max(w - 6, 0) * max(h - 6, 0))
 
 
-class KeyframeExtractor:
+class KeyframeExtractor(_stage.StageHandle):
     """KeyFrame's constructor on the MI355X: FAST, BRIEF and the lift for many images per call"""
+    PREFIX, N_MS = "isv_kf", 7
 
     def __init__(self, max_items=1, max_width=752, max_height=480, **kw):
-        self.lib = backend.load_library()
-        _bind(self.lib)
         self.cfg = make_config(max_items, max_width, max_height, **kw)
-        self.h = C.c_void_p()
-        rc = self.lib.isv_kf_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise backend.BackendError(f"isv_kf_create: {backend.STATUS.get(rc, rc)} (a MI355X and the HIP extension are required; there is no CPU path)")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.isv_kf_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(_bind, C.byref(self.cfg), why=" (a MI355X and the HIP extension are required; there is no CPU path)")
 
     def extract_batch(self, items):
         """items: KfItem list -> (isv_kf_result_t list, KfArrays list).  The arrays are pre-filled with FILL bytes; a refused item's
@@ -183,44 +162,35 @@ class KeyframeExtractor:
         n = len(items)
         res = (isv_kf_result_t * max(n, 1))()
         ptrs = (C.POINTER(isv_kf_item_t) * max(n, 1))(*[C.pointer(it.c) for it in items])
-        caps = [max(keypoint_capacity(self.cfg, it), 1) for it in items]
-        nps = [max(it.c.n_points, 1) for it in items]
-        br = [np.full((c, 4), FILL * 0x0101010101010101, dtype=np.uint64) for c in caps]
-        uv = [np.full((c, 2), FILL, dtype=np.uint8).repeat(4, axis=1).view(np.float32) for c in caps]
-        nm = [np.full((c, 2), FILL, dtype=np.uint8).repeat(4, axis=1).view(np.float32) for c in caps]
-        sc = [np.full(c, FILL, dtype=np.uint8) for c in caps]
-        wb = [np.full((c, 4), FILL * 0x0101010101010101, dtype=np.uint64) for c in nps]
+        caps = [keypoint_capacity(self.cfg, it) for it in items]
+        br = [filled(c, 4, np.uint64) for c in caps]
+        uv = [filled(c, 2, np.float32) for c in caps]
+        nm = [filled(c, 2, np.float32) for c in caps]
+        sc = [filled(c, 1, np.uint8).reshape(-1) for c in caps]
+        wb = [filled(it.c.n_points, 4, np.uint64) for it in items]
         arr = lambda t, xs: (t * max(n, 1))(*[a.ctypes.data_as(t) for a in xs])
         rc = self.lib.isv_kf_extract_batch(self.h, n, ptrs, res, arr(_u64p, br), arr(_f32p, uv), arr(_f32p, nm), arr(_u8p, sc), arr(_u64p, wb))
-        if rc != 0:
-            msg = self.lib.isv_kf_last_error(self.h)
-            raise backend.BackendError(f"isv_kf_extract_batch: {backend.STATUS.get(rc, rc)} {msg.decode() if msg else ''}")
+        self._check(rc, "isv_kf_extract_batch", with_last_error=True)
         out = list(res)[:n]
         arrays = []
         for i, r in enumerate(out):
             k, p = (r.n_keypoints, r.n_points) if r.status == ISV_KF_OK else (0, 0)
             for a in (br[i], uv[i], nm[i], sc[i]):
-                assert (a.view(np.uint8).reshape(len(a), -1)[k:] == FILL).all(), "written past an item's count"
-            assert (wb[i].view(np.uint8).reshape(len(wb[i]), -1)[p:] == FILL).all(), "written past an item's points"
+                assert untouched(a, k), "written past an item's count"
+            assert untouched(wb[i], p), "written past an item's points"
             arrays.append(KfArrays(br[i][:k], uv[i][:k], nm[i][:k], sc[i][:k], wb[i][:p]))
         return out, arrays
 
     def read_back(self, index, width, height):
         """the blurred image and the FAST score map of item `index` of the last call (debug entry, csrc/isv_keyframe.h)"""
         blur, smap = np.zeros((height, width), np.uint8), np.zeros((height, width), np.uint8)
-        rc = self.lib.isv_internal_kf_read_back(self.h, index, blur.ctypes.data_as(_u8p), smap.ctypes.data_as(_u8p))
-        if rc != 0:
-            raise backend.BackendError(f"isv_internal_kf_read_back: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_internal_kf_read_back(self.h, index, blur.ctypes.data_as(_u8p), smap.ctypes.data_as(_u8p)), "isv_internal_kf_read_back")
         return blur, smap
 
     def last_ms(self):
         """(whole call, k_kf_blur, k_kf_fast, k_kf_select, k_kf_brief, the upload, the host's packing) milliseconds of the last successful
         call"""
-        ms = (C.c_double * 7)()
-        rc = self.lib.isv_kf_last_ms(self.h, ms)
-        if rc != 0:
-            raise backend.BackendError(f"isv_kf_last_ms: {backend.STATUS.get(rc, rc)}")
-        return tuple(ms)
+        return super().last_ms()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import backend, posegraph, synth
+from . import _stage, backend, posegraph, synth
 
 (ISV_LOOP_OK, ISV_LOOP_FEW_MATCHES, ISV_LOOP_UNDEFINED_POSE, ISV_LOOP_PNP_FAILED, ISV_LOOP_GATE, ISV_LOOP_PLANAR, ISV_LOOP_CAPACITY,
  ISV_LOOP_INPUT) = range(8)
@@ -81,13 +81,8 @@ class LoopPair:
         return self.c.n_points
 
 
-_bound = False
-
-
+@_stage.bind_once("loop")
 def _bind(lib):
-    global _bound
-    if _bound:
-        return
     vp = C.c_void_p
     lib.isv_loop_create.argtypes = [C.POINTER(isv_loop_config_t), C.POINTER(vp)]
     lib.isv_loop_destroy.argtypes = [vp]; lib.isv_loop_destroy.restype = None
@@ -96,7 +91,6 @@ def _bind(lib):
                                           C.POINTER(_i32p), C.POINTER(_i32p), C.POINTER(_i32p)]
     lib.isv_loop_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.isv_loop_apply.argtypes = [C.POINTER(isv_loop_result_t), C.POINTER(posegraph.isv_pg_keyframe_t)]
-    _bound = True
 
 
 def apply(result, keyframe, lib=None):
@@ -108,28 +102,13 @@ def apply(result, keyframe, lib=None):
         raise backend.BackendError(f"isv_loop_apply: {backend.STATUS.get(rc, rc)}")
 
 
-class LoopVerifier:
+class LoopVerifier(_stage.StageHandle):
     """KeyFrame::findConnection on the MI355X: one workgroup per keyframe pair in each of two kernels"""
+    PREFIX, N_MS = "isv_loop", 3
 
     def __init__(self, max_pairs=1, max_points=256, max_keypoints=2048, **kw):
-        self.lib = backend.load_library()
-        _bind(self.lib)
         self.cfg = make_config(max_pairs, max_points, max_keypoints, **kw)
-        self.h = C.c_void_p()
-        rc = self.lib.isv_loop_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise backend.BackendError(f"isv_loop_create: {backend.STATUS.get(rc, rc)} (a MI355X and the HIP extension are required; there is no CPU path)")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.isv_loop_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(_bind, C.byref(self.cfg), why=" (a MI355X and the HIP extension are required; there is no CPU path)")
 
     def verify_batch(self, pairs, per_point=False):
         """pairs: LoopPair list -> isv_loop_result_t list; with per_point also (match_index, match_dist, inlier), each a list of
@@ -143,9 +122,7 @@ class LoopVerifier:
             outs = [[np.full(max(p.c.n_points, 1), -2, dtype=np.int32) for p in pairs] for _ in range(3)]
             args = [(_i32p * max(n, 1))(*[a.ctypes.data_as(_i32p) for a in o]) for o in outs]
         rc = self.lib.isv_loop_verify_batch(self.h, n, ptrs, res, *args)
-        if rc != 0:
-            msg = self.lib.isv_loop_last_error(self.h)
-            raise backend.BackendError(f"isv_loop_verify_batch: {backend.STATUS.get(rc, rc)} {msg.decode() if msg else ''}")
+        self._check(rc, "isv_loop_verify_batch", with_last_error=True)
         out = list(res)[:n]
         if not per_point:
             return out
@@ -153,11 +130,7 @@ class LoopVerifier:
 
     def last_ms(self):
         """(whole call, k_loop_match, k_loop_pnp) milliseconds of the last successful call"""
-        ms = (C.c_double * 3)()
-        rc = self.lib.isv_loop_last_ms(self.h, ms)
-        if rc != 0:
-            raise backend.BackendError(f"isv_loop_last_ms: {backend.STATUS.get(rc, rc)}")
-        return tuple(ms)
+        return super().last_ms()
 
     def apply(self, result, keyframe):
         apply(result, keyframe, self.lib)

@@ -9,7 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import backend
+from . import _stage
+from ._stage import FILL, filled, untouched
 from .keyframe import EUROC
 
 ISV_TRK_OK, ISV_TRK_CAPACITY, ISV_TRK_INPUT = range(3)
@@ -96,14 +97,8 @@ class TrkArrays:
         return (self.cur_pts[m], self.cur_un_pts[m]) + tuple(np.asarray(o)[m] for o in others)
 
 
-_bound = False
-FILL = 0xA5                                # the pattern the output arrays are pre-filled with
-
-
+@_stage.bind_once("trk")
 def _bind(lib):
-    global _bound
-    if _bound:
-        return
     vp = C.c_void_p
     lib.isv_trk_create.argtypes = [C.POINTER(isv_trk_config_t), C.POINTER(vp)]
     lib.isv_trk_destroy.argtypes = [vp]; lib.isv_trk_destroy.restype = None
@@ -113,31 +108,15 @@ def _bind(lib):
     lib.isv_trk_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.isv_trk_slot_reset.argtypes = [vp, C.c_int32]
     lib.isv_internal_trk_read_level.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _u8p, _i32p, _i32p]
-    _bound = True
 
 
-class Tracker:
+class Tracker(_stage.StageHandle):
     """FeatureTracker::readImage's optical flow on the MI355X: many sequences per call, one slot per sequence"""
+    PREFIX, N_MS = "isv_trk", 5
 
     def __init__(self, max_slots=1, max_items=None, max_width=752, max_height=480, **kw):
-        self.lib = backend.load_library()
-        _bind(self.lib)
         self.cfg = make_config(max_slots, max_slots if max_items is None else max_items, max_width, max_height, **kw)
-        self.h = C.c_void_p()
-        rc = self.lib.isv_trk_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            self.h = None
-            raise backend.BackendError(f"isv_trk_create: {backend.STATUS.get(rc, rc)} (a MI355X and the HIP extension are required; there is no CPU path)")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.isv_trk_destroy(self.h); self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(_bind, C.byref(self.cfg), why=" (a MI355X and the HIP extension are required; there is no CPU path)")
 
     def track_batch(self, items):
         """items: TrkItem list -> (isv_trk_result_t list, TrkArrays list).  The arrays are pre-filled with FILL bytes; a refused item's
@@ -145,50 +124,38 @@ class Tracker:
         n = len(items)
         res = (isv_trk_result_t * max(n, 1))()
         ptrs = (C.POINTER(isv_trk_item_t) * max(n, 1))(*[C.pointer(it.c) for it in items])
-        nps = [max(it.c.n_points, 1) for it in items]
-        cp = [np.full((c, 2), FILL, dtype=np.uint8).repeat(4, axis=1).view(np.float32) for c in nps]
-        un = [np.full((c, 2), FILL, dtype=np.uint8).repeat(4, axis=1).view(np.float32) for c in nps]
-        er = [np.full((c, 1), FILL, dtype=np.uint8).repeat(4, axis=1).view(np.float32).reshape(c) for c in nps]
-        fl = [np.full(c, FILL, dtype=np.uint8) for c in nps]
+        nps = [it.c.n_points for it in items]
+        cp = [filled(c, 2, np.float32) for c in nps]
+        un = [filled(c, 2, np.float32) for c in nps]
+        er = [filled(c, 1, np.float32).reshape(-1) for c in nps]
+        fl = [filled(c, 1, np.uint8).reshape(-1) for c in nps]
         arr = lambda t, xs: (t * max(n, 1))(*[a.ctypes.data_as(t) for a in xs])
         rc = self.lib.isv_trk_track_batch(self.h, n, ptrs, res, arr(_f32p, cp), arr(_u8p, fl), arr(_f32p, er), arr(_f32p, un))
-        if rc != 0:
-            msg = self.lib.isv_trk_last_error(self.h)
-            raise backend.BackendError(f"isv_trk_track_batch: {backend.STATUS.get(rc, rc)} {msg.decode() if msg else ''}")
+        self._check(rc, "isv_trk_track_batch", with_last_error=True)
         out = list(res)[:n]
         arrays = []
         for i, r in enumerate(out):
             p = r.n_points if r.status == ISV_TRK_OK else 0
             for a in (cp[i], un[i], er[i], fl[i]):
-                assert (a.view(np.uint8).reshape(len(a), -1)[p:] == FILL).all(), "written past an item's points, or into a refused item's arrays"
+                assert untouched(a, p), "written past an item's points, or into a refused item's arrays"
             arrays.append(TrkArrays(cp[i][:p], fl[i][:p], er[i][:p], un[i][:p]))
         return out, arrays
 
     def slot_reset(self, slot):
-        rc = self.lib.isv_trk_slot_reset(self.h, slot)
-        if rc != 0:
-            raise backend.BackendError(f"isv_trk_slot_reset: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_trk_slot_reset(self.h, slot), "isv_trk_slot_reset")
 
     def read_level(self, slot, level, which=0):
         """one pyramid level of a slot (debug entry, csrc/isv_tracker.h): which = 0 the resident pyramid (the last cur image's),
         1 the last prev image's"""
         w, h = C.c_int32(), C.c_int32()
-        rc = self.lib.isv_internal_trk_read_level(self.h, slot, which, level, None, C.byref(w), C.byref(h))
-        if rc != 0:
-            raise backend.BackendError(f"isv_internal_trk_read_level: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_internal_trk_read_level(self.h, slot, which, level, None, C.byref(w), C.byref(h)), "isv_internal_trk_read_level")
         out = np.zeros((h.value, w.value), np.uint8)
-        rc = self.lib.isv_internal_trk_read_level(self.h, slot, which, level, out.ctypes.data_as(_u8p), None, None)
-        if rc != 0:
-            raise backend.BackendError(f"isv_internal_trk_read_level: {backend.STATUS.get(rc, rc)}")
+        self._check(self.lib.isv_internal_trk_read_level(self.h, slot, which, level, out.ctypes.data_as(_u8p), None, None), "isv_internal_trk_read_level")
         return out
 
     def last_ms(self):
         """(whole call, the pyramid kernels, k_trk_track, the upload, the host's packing) milliseconds of the last successful call"""
-        ms = (C.c_double * 5)()
-        rc = self.lib.isv_trk_last_ms(self.h, ms)
-        if rc != 0:
-            raise backend.BackendError(f"isv_trk_last_ms: {backend.STATUS.get(rc, rc)}")
-        return tuple(ms)
+        return super().last_ms()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
