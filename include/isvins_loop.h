@@ -14,9 +14,10 @@
  * it) and, like them, never read.
  *
  * cv::solvePnPRansac is RESTATED from OpenCV 3.2.0 as published (calib3d: solvepnp.cpp, ptsetreg.cpp, epnp.cpp,
- * calibration.cpp); OpenCV is not available to this project, so the restatement cannot be checked against it.  The CPU
+ * calibration.cpp); OpenCV is not available to this project, so the restatement cannot be checked against its source.  The CPU
  * restatement tests/native/isv_loop_oracle.c runs the same shared text (is-vins_amd/csrc/isv_loop_common.h) as the kernel and
- * pins the GPU, not OpenCV.
+ * pins the GPU, not the definition; an independent 40-digit reading of the definitions cited below (tests/loop_highprec.py) pins
+ * both the restatement and the kernel.
  *   RANSACPointSetRegistrator::run   modelPoints 5, ransac_iterations at most, a fresh RNG((uint64)-1), getSubset's distinct
  *                                    draws, a model kept when its inlier count > max(best, 4), RANSACUpdateNumIters; the error of
  *                                    a point is the squared float32 distance of its float32 projection, compared in float32

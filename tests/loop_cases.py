@@ -3,7 +3,7 @@ tests/test_gpu_loop.py (k_loop_match / k_loop_pnp against the restatement).  Sha
 old descriptors through tiles of T = 512 with four wavefronts of 64 lanes per workgroup, k_loop_pnp runs 64 hypotheses per chunk."""
 import numpy as np
 
-from isvins_amd import loop
+from isvins_amd import loop, synth
 
 T = 512                      # k_loop_match's tile (kTile in is-vins_amd/csrc/isv_loop.hip)
 WAVES = 4                    # its wavefronts per workgroup
@@ -60,7 +60,41 @@ def scene_cases():
          ("p5", dict(seed=20, n_points=WAVES + 1, n_keypoints=70)), ("p1", dict(seed=21, n_points=1, n_keypoints=1)),
          ("p0", dict(seed=22, n_points=0, n_keypoints=40)), ("k0", dict(seed=23, n_points=30, n_keypoints=0, n_matchable=0)),
          ("k1", dict(seed=24, n_points=30, n_keypoints=1, n_matchable=1))]
-    return c
+    return c + CHUNK_EDGES
+
+
+# k_loop_pnp's chunk edges and lane loops (64 hypotheses a chunk, 64 lanes), found by a seed search with the CPU restatement; the
+# unmatchable window points stand between the matchable ones (make_scene).  tests/loop_highprec_cases.py has the table.  The old
+# keyframe stands at seed 0's pose: make_loop_scene moves it by 0.1 m and 0.1 rad per seed, which at seed 1000 puts float32 points
+# 150 m from the origin and makes the DLT's 12 x 12 system needlessly ill-conditioned.
+OLD_POSE = (synth._rot_zyx(0.3, 0.05, -0.04), np.array([1.0, -2.0, 0.5]))
+CHUNK_EDGES = [
+    ("stop64", dict(seed=1006, n_points=43, n_matchable=29, n_keypoints=70, outliers=0.41, interleave=True, old_pose=OLD_POSE)),
+    ("stop65", dict(seed=1017, n_points=60, n_matchable=41, n_keypoints=129, outliers=0.41, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+    ("keep2_f63", dict(seed=1087, n_points=190, n_matchable=158, n_keypoints=400, outliers=0.6, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+    ("late129", dict(seed=1644, n_points=60, n_matchable=48, n_keypoints=150, outliers=0.62, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+    ("f64", dict(seed=1005, n_points=93, n_matchable=70, n_keypoints=300, outliers=0.08, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+    ("f65", dict(seed=1005, n_points=96, n_matchable=72, n_keypoints=300, outliers=0.08, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+    ("floor4", dict(seed=171, n_points=24, n_matchable=16, n_keypoints=80, outliers=0.75, interleave=True, old_pose=OLD_POSE)),
+    ("f129", dict(seed=1013, n_points=189, n_matchable=142, n_keypoints=300, outliers=0.08, pixel_noise=NOISE, interleave=True, old_pose=OLD_POSE)),
+]
+
+
+def make_scene(kw):
+    """loop.make_loop_scene(**kw); with interleave=True the window points are reordered so that the unmatchable ones stand between
+    the matchable ones (make_loop_scene puts the matchable first): a matched point's window index `src` then differs from its
+    position in the match list, which is what the inlier mask and the compaction are indexed by"""
+    kw = dict(kw)
+    if not kw.pop("interleave", False):
+        return loop.make_loop_scene(**kw)
+    pair, tr = loop.make_loop_scene(**kw)
+    n, nm = pair.c.n_points, kw["n_matchable"]
+    keys = [(j + 0.5) / nm for j in range(nm)] + [(u + 0.25) / (n - nm) for u in range(n - nm)]
+    order = np.argsort(keys, kind="stable")
+    out = loop.LoopPair(pair.window_brief[order], pair.point_3d[order], pair.point_2d_norm[order], pair.brief, pair.keypoints_norm,
+                        pair.origin_vio_T, pair.origin_vio_R, pair.c.old_index)
+    tr = dict(tr, is_outlier=tr["is_outlier"][order], counterpart=tr["counterpart"][order])
+    return out, tr
 
 
 def refusal_cases():
@@ -88,7 +122,7 @@ def all_pairs():
     if _cache is None:
         out = [(n, p, None) for n, p, _ in match_cases()]
         for n, kw in scene_cases():
-            p, tr = loop.make_loop_scene(**kw)
+            p, tr = make_scene(kw)
             out.append((n, p, tr))
         out += [(n, p, None) for n, p, _ in refusal_cases()]
         _cache = out

@@ -31,6 +31,7 @@ def build(tmpdir, opt="-O2"):
     lib.isvo_loop_verify.argtypes = [cfgp, pairp, resp, _ip, _ip, _ip]
     lib.isvo_lp_iterative.argtypes = [C.c_int, _dp, _dp, _dp, _ip]
     lib.isvo_lp_epnp.argtypes = [C.c_int, _dp, _dp, _dp, _dp]; lib.isvo_lp_epnp.restype = None
+    lib.isvo_lp_epnp_basis.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]; lib.isvo_lp_epnp_basis.restype = None
     lib.isvo_eig_jacobi_sym.argtypes = [C.c_int, _dp, _dp, _dp]; lib.isvo_eig_jacobi_sym.restype = None
     lib.isvo_rodrigues_v2m.argtypes = [_dp, _dp]; lib.isvo_rodrigues_v2m.restype = None
     lib.isvo_lp_point_error.argtypes = [_dp, _dp, _fp, _fp]; lib.isvo_lp_point_error.restype = C.c_double
@@ -74,6 +75,14 @@ def epnp(lib, X, uv):
     R, t = np.zeros(9), np.zeros(3)
     lib.isvo_lp_epnp(len(X), _d(X), _d(uv), _d(R), _d(t))
     return R.reshape(3, 3), t
+
+
+def epnp_basis(lib, X, uv):
+    """lp_epnp and the basis it used -> (R, t, control points [4][3], eigenvectors [4][12], smallest eigenvalue first)"""
+    X = np.ascontiguousarray(X, dtype=np.float64); uv = np.ascontiguousarray(uv, dtype=np.float64)
+    R, t, cws, vv = np.zeros(9), np.zeros(3), np.zeros((4, 3)), np.zeros((4, 12))
+    lib.isvo_lp_epnp_basis(len(X), _d(X), _d(uv), _d(R), _d(t), _d(cws), _d(vv))
+    return R.reshape(3, 3), t, cws, vv
 
 
 def iterative(lib, X, uv):

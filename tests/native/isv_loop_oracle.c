@@ -135,6 +135,27 @@ void isvo_lp_epnp(int n, const double *X, const double *uv, double *R, double *t
     double work[288];
     lp_epnp(n, X, uv, R, t, work);
 }
+/* debug entry for the 40-digit EPnP stage test (tests/loop_highprec.py): lp_epnp's result and the basis it used.  vv [4][12]: the
+ * eigenvectors of the four smallest eigenvalues, smallest first, read back from lp_epnp's work array (it leaves them at work + 144).
+ * cws [4][3]: the control points, by choose_control_points' statements on the same input (the same routine on the same numbers, so
+ * the same axes and signs).  The shared header is not touched: the kernel's code object cannot change. */
+void isvo_lp_epnp_basis(int n, const double *X, const double *uv, double *R, double *t, double *cws, double *vv) {
+    double work[288], CC[9], w3[3], V3[9];
+    lp_epnp(n, X, uv, R, t, work);
+    for (int i = 0; i < 4; i++) for (int k = 0; k < 12; k++) vv[12 * i + k] = work[144 + 12 * k + (11 - i)];
+    for (int k = 0; k < 3; k++) cws[k] = 0.0;
+    for (int i = 0; i < n; i++) for (int k = 0; k < 3; k++) cws[k] += X[3 * i + k];
+    for (int k = 0; k < 3; k++) cws[k] /= n;
+    for (int k = 0; k < 9; k++) CC[k] = 0.0;
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < 3; j++)
+            for (int k = 0; k < 3; k++) CC[3 * j + k] += (X[3 * i + j] - cws[j]) * (X[3 * i + k] - cws[k]);
+    svd_jacobi(3, CC, w3, 0, V3);
+    for (int i = 1; i < 4; i++) {
+        const double s = sqrt(w3[i - 1] / n);
+        for (int j = 0; j < 3; j++) cws[3 * i + j] = cws[j] + s * V3[3 * j + (i - 1)];
+    }
+}
 void isvo_eig_jacobi_sym(int n, double *A, double *w, double *V) { eig_jacobi_sym(n, A, w, V); }
 void isvo_rodrigues_v2m(const double *rv, double *R) { rodrigues_v2m(rv, R, NULL); }
 void isvo_rodrigues_v2m_J(const double *rv, double *R, double *J) { rodrigues_v2m(rv, R, J); }   /* J: 3 x 9, d R / d r_i */

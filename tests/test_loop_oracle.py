@@ -167,12 +167,21 @@ def test_every_status(lib):
 
 def test_ransac_shapes_of_the_case_list(lib):
     """the GPU list holds a RANSAC that stops inside its first 64-hypothesis chunk, one that runs all 100 iterations (two chunks),
-    one that keeps no model, and 16 / 17 / 64 / 65 / 200 matches"""
+    one that keeps no model, 16 / 17 / 64 / 65 / 200 matches, and the chunk edges below"""
     rs = {n: loop_oracle.verify(lib, CFG, p)[0] for n, p, _ in loop_cases.all_pairs()}
     assert rs["exact0"].ransac_iters < 64 and rs["out60_noise"].ransac_iters == 100
     assert rs["all_outliers"].ransac_iters == 100 and rs["all_outliers"].ransac_inliers == 0 and rs["all_outliers"].n_final == 0
     assert [rs[n].n_matched for n in ("m16", "m17", "m64", "m65", "m200")] == [16, 17, 64, 65, 200]
     assert 10 <= rs["l1_10"].n_matched and rs["l1_15"].n_matched == 15 and rs["few9"].n_matched == 9
+    # the chunk edges (tests/loop_highprec_cases.py has the table): a stop at hypothesis 64, the last of the first chunk; at 65, where
+    # the second chunk is drawn with one hypothesis; the cap with the final model kept in the second chunk; no model with four inliers
+    # at the keep rule's floor; 63 / 64 / 65 / 129 final inliers with the unmatchable window points interleaved
+    assert (rs["stop64"].n_matched, rs["stop64"].ransac_inliers, rs["stop64"].ransac_iters) == (29, 17, 64)
+    assert (rs["stop65"].n_matched, rs["stop65"].ransac_inliers, rs["stop65"].ransac_iters) == (41, 24, 65)
+    assert (rs["keep2_f63"].n_matched, rs["keep2_f63"].ransac_iters, rs["keep2_f63"].n_final) == (158, 100, 63)
+    assert (rs["floor4"].n_matched, rs["floor4"].ransac_iters, rs["floor4"].ransac_inliers) == (16, 100, 0)
+    assert [rs[n].n_final for n in ("f64", "f65", "f129")] == [64, 65, 129] and [rs[n].n_matched for n in ("f64", "f65", "f129")] == [70, 72, 142]
+    assert rs["late129"].n_matched == 48 and rs["late129"].ransac_iters == 100        # (its event needs ransac_iterations = 129)
 
 
 # ---------------------------------------------------------------- quirks
