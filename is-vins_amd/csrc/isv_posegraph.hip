@@ -17,19 +17,8 @@
 // recurrence on the same envelope (never a dense inverse).
 // This is latency-bound sparse work (dependent 6x6 block recurrences through L2); it is not reshaped into dense GEMMs.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <functional>
-#include <mutex>
-#include <thread>
 #include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "../../include/isvins_posegraph.h"
+#include "isv_pgo_host.h"      // the host half of the call (and PgEdge / PgGraph: isv_pgo_types.h)
 #include "isv_device_math.h"
 #include "isv_prior_factor.h"
 
@@ -40,21 +29,6 @@
 #define PG_LSYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
 // make this wavefront's global stores visible to its own later loads (other lanes read what a lane wrote)
 #define PG_GSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
-
-struct PgEdge {                  // one residual block
-    int32_t kind;                // 0 roll/pitch (a), 1 relative pose (a -> b), 2 loop closure (a = matched keyframe, b = the one that closed)
-    int32_t a, b;                // local pose indices
-    int32_t fa, fb;              // their free (non-constant) indices, -1 if constant
-    int32_t dim, robust, _pad;
-    double meas_t[3], meas_R[9], sqrt_info[36];
-};
-
-struct PgGraph {                 // offsets of one pose graph into the handle's pools
-    int32_t P1, nf, ne, nblk;    // poses, free poses, residual blocks, skyline blocks
-    int32_t pose0, free0, edge0, blk0, adj0, col0, vec0, _pad;
-    int32_t max_iter, _pad2;
-    double huber;
-};
 
 struct PgDev {
     PgGraph *graphs;
@@ -833,41 +807,34 @@ __global__ __launch_bounds__(64 * NW) void k_pgo(PgDev dv) {
 
 // =====================================================================================================================
 // host side
-// the STRUCTURE of one graph slot as the last call analysed it (round 4: PoseGraph::optimizeCS re-optimises a graph that grew by
-// at most one keyframe since the last loop closure; a batch that is optimised again -- the benchmark, a replay -- has the same
-// topology slot by slot): parameter-block map, free indices, adjacency, skyline, column patterns and the edges' integer fields.
-// Keyed by a hash of everything the structure depends on; the numbers (poses, measurements, sqrt_info) are refreshed every call.
-struct PgEdgeTpl { int32_t kind, a, b, fa, fb, dim, robust, src; };     // src: the keyframe whose factor this residual block is
-struct PgStructCache {
-    uint64_t key = 0; bool valid = false;
-    std::vector<uint64_t> raw;                    // the key tuple itself: a hash match alone would reuse another topology's structure on a collision
-    std::vector<int> loc;
-    int cur_pos = -1, n_loops = 0;
-    int32_t P1 = 0, nf = 0, nblk = 0;
-    std::vector<int32_t> free_of, adj_ptr, adj, start, rowptr, colptr, colrows;
-    std::vector<PgEdgeTpl> edges;
-};
+// (structure record, analysis, numbers, the table of the call's arrays, layout, write-back, thread team and the pipeline's control
+//  flow: isv_pgo_host.h.  Here: the handle, the HIP calls of a chunk and the entry points.)
 struct isv_pgo {
-    std::vector<PgStructCache> cache;             // [max_graphs]
+    std::vector<PgStructure> cache;               // [max_graphs] the structure of every graph slot as the last call analysed it
     int64_t cache_hits = 0;
     isv_pgo_config_t cfg;
     std::string err;
     int device = 0, n_cus = 256;
+    // No work is ever put on `stream`, but it is NOT dead: created ahead of the four chunk streams, it shifts which hardware queues
+    // those land on.  Measured with and without it, all else equal, in a process that already holds other streams (bench.py --full,
+    // 1024 graphs, cached calls): last enqueue -> last drain 17.4 / 22.7 ms with it, 30.8 / 33.3 ms without; k_pgo's span 19.3 ms
+    // against 31.2-31.7; the call 29.8-30.9 ms against 39.7-41.2.  In a process of its own (scripts/pgo_probe.py) there is no
+    // difference.  It stays until the chunk streams' placement is understood.
     hipStream_t stream = nullptr;
     PgDev d{};
     std::vector<void *> allocs;
-    size_t cap_pose = 0, cap_edge = 0, cap_blk = 0, cap_adj = 0, cap_col = 0;
+    PgCaps cap{};
     void *pin = nullptr; size_t pin_cap = 0;      // pinned staging of a batch call's arrays (grown on demand, kept)
-    hipEvent_t ev[2] = {nullptr, nullptr};       // (unused since the chunked launches; kept for the destroy loop)
-    // a batch call goes to the device in up to PG_CHUNKS chunks of graphs, each on a stream of its own: chunk c + 1 is assembled and
+    // a batch call goes to the device in up to PG_MAX_CHUNKS chunks of graphs, each on a stream of its own: chunk c + 1 is assembled and
     // copied while chunk c is being solved, and chunk c is written back while chunk c + 1 still runs (round 4)
-    static constexpr int PG_CHUNKS = 4;
-    hipStream_t cstream[PG_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t kev[PG_CHUNKS][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};     // around every chunk's k_pgo
+    hipStream_t cstream[PG_MAX_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t kev[PG_MAX_CHUNKS][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};     // around every chunk's k_pgo
     double last_kernel_ms = -1;                   // first chunk's kernel start -> last chunk's kernel end of the last call
     double last_blocks = 0;                       // skyline blocks of the last batch (all graphs)
 };
 
+// (msg) = "<call>: <HIP's error string>" and return ISV_ERR_DEVICE when a HIP call fails
+#define PMSG(msg, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (msg) = std::string(#call) + ": " + hipGetErrorString(e_); return ISV_ERR_DEVICE; } } while (0)
 #define PCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return ISV_ERR_DEVICE; } } while (0)
 template <typename T> static int pal(isv_pgo *h, T **p, size_t n) {
     void *q = nullptr;
@@ -878,7 +845,7 @@ template <typename T> static int pal(isv_pgo *h, T **p, size_t n) {
 #define PTRY(x) do { int rc_ = (x); if (rc_ != ISV_OK) return rc_; } while (0)
 
 extern "C" const char *isv_pgo_last_error(const isv_pgo_t *h) { return h ? h->err.c_str() : "null handle"; }
-// measurement: duration of k_pgo in the last optimize call (HIP events on the handle's stream) and the number of 6x6 skyline
+// measurement: duration of k_pgo in the last optimize call (HIP events on the chunks' streams) and the number of 6x6 skyline
 // blocks its graphs held
 extern "C" int64_t isv_pgo_structure_cache_hits(const isv_pgo_t *h) { return h ? h->cache_hits : 0; }
 extern "C" int isv_pgo_last_kernel_ms(isv_pgo_t *h, double *ms, double *skyline_blocks) {
@@ -892,7 +859,6 @@ extern "C" void isv_pgo_destroy(isv_pgo_t *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     for (void *p : h->allocs) (void)hipFree(p);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     for (auto &cs : h->cstream) if (cs) (void)hipStreamDestroy(cs);
@@ -906,21 +872,22 @@ static int pgo_create_impl(isv_pgo *h) {
     if (ndev <= 0) { h->err = "no HIP device"; return ISV_ERR_DEVICE; }
     PCHK(h, hipGetDevice(&h->device));
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cu > 0) h->n_cus = cu; else (void)hipGetLastError(); }
-    PCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    PCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));       // (the spacer: see isv_pgo::stream)
     for (auto &cs : h->cstream) PCHK(h, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     for (auto &ke : h->kev) for (auto &e : ke) PCHK(h, hipEventCreate(&e));
     const size_t G = h->cfg.max_graphs, K = h->cfg.max_keyframes;
-    h->cap_pose = G * K; h->cap_edge = G * 3 * K; h->cap_blk = G * (2 * K + (size_t)h->cfg.max_loop_blocks);
-    h->cap_adj = 2 * h->cap_edge; h->cap_col = h->cap_blk;
+    PgCaps &cap = h->cap;
+    cap.pose = G * K; cap.edge = G * 3 * K; cap.blk = G * (2 * K + (size_t)h->cfg.max_loop_blocks);
+    cap.adj = 2 * cap.edge; cap.col = cap.blk;
     PgDev &d = h->d;
-    PTRY(pal(h, &d.graphs, G)); PTRY(pal(h, &d.pose, h->cap_pose * 7)); PTRY(pal(h, &d.cand, h->cap_pose * 7)); PTRY(pal(h, &d.free_of, h->cap_pose));
-    PTRY(pal(h, &d.edges, h->cap_edge)); PTRY(pal(h, &d.eres, h->cap_edge * 6)); PTRY(pal(h, &d.ejac, h->cap_edge * 72)); PTRY(pal(h, &d.red, h->cap_edge * 6)); PTRY(pal(h, &d.Bt, h->cap_pose * 36));
-    PTRY(pal(h, &d.adj_ptr, h->cap_pose + G)); PTRY(pal(h, &d.adj, h->cap_adj));
-    PTRY(pal(h, &d.start, h->cap_pose)); PTRY(pal(h, &d.rowptr, h->cap_pose + G)); PTRY(pal(h, &d.colptr, h->cap_pose + G)); PTRY(pal(h, &d.colrows, h->cap_col));
-    PTRY(pal(h, &d.H, h->cap_blk * 36)); PTRY(pal(h, &d.L, h->cap_blk * 36)); PTRY(pal(h, &d.Z, h->cap_blk * 36));
-    PTRY(pal(h, &d.scale, h->cap_pose * 6)); PTRY(pal(h, &d.diag, h->cap_pose * 6)); PTRY(pal(h, &d.grad, h->cap_pose * 6));
-    PTRY(pal(h, &d.step, h->cap_pose * 6)); PTRY(pal(h, &d.ysol, h->cap_pose * 6));
-    PTRY(pal(h, &d.cov, h->cap_pose * 36)); PTRY(pal(h, &d.res, G));
+    PTRY(pal(h, &d.graphs, G)); PTRY(pal(h, &d.pose, cap.pose * 7)); PTRY(pal(h, &d.cand, cap.pose * 7)); PTRY(pal(h, &d.free_of, cap.pose));
+    PTRY(pal(h, &d.edges, cap.edge)); PTRY(pal(h, &d.eres, cap.edge * 6)); PTRY(pal(h, &d.ejac, cap.edge * 72)); PTRY(pal(h, &d.red, cap.edge * 6)); PTRY(pal(h, &d.Bt, cap.pose * 36));
+    PTRY(pal(h, &d.adj_ptr, cap.pose + G)); PTRY(pal(h, &d.adj, cap.adj));
+    PTRY(pal(h, &d.start, cap.pose)); PTRY(pal(h, &d.rowptr, cap.pose + G)); PTRY(pal(h, &d.colptr, cap.pose + G)); PTRY(pal(h, &d.colrows, cap.col));
+    PTRY(pal(h, &d.H, cap.blk * 36)); PTRY(pal(h, &d.L, cap.blk * 36)); PTRY(pal(h, &d.Z, cap.blk * 36));
+    PTRY(pal(h, &d.scale, cap.pose * 6)); PTRY(pal(h, &d.diag, cap.pose * 6)); PTRY(pal(h, &d.grad, cap.pose * 6));
+    PTRY(pal(h, &d.step, cap.pose * 6)); PTRY(pal(h, &d.ysol, cap.pose * 6));
+    PTRY(pal(h, &d.cov, cap.pose * 36)); PTRY(pal(h, &d.res, G));
     return ISV_OK;
 }
 
@@ -936,89 +903,6 @@ extern "C" int isv_pgo_create(const isv_pgo_config_t *cfg, isv_pgo_t **out) {
     *out = h;
     return ISV_OK;
 }
-
-// ---- small host 3x3 / SO(3) arithmetic for the write-back (RelativePoseFactor::update, drift) ----------------------
-namespace {
-struct HQ { double w, x, y, z; };
-void h_q2R(HQ q, double *R) {
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z, twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy; R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-HQ h_R2q(const double *m) {      // Eigen matrix -> quaternion
-    HQ q; double t = m[0] + m[4] + m[8];
-    if (t > 0) { t = std::sqrt(t + 1.0); q.w = 0.5 * t; t = 0.5 / t; q.x = (m[7] - m[5]) * t; q.y = (m[2] - m[6]) * t; q.z = (m[3] - m[1]) * t; return q; }
-    int i = 0; if (m[4] > m[0]) i = 1; if (m[8] > m[i * 4]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = std::sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
-    double v[3]; v[i] = 0.5 * t; t = 0.5 / t;
-    q.w = (m[k * 3 + j] - m[j * 3 + k]) * t; v[j] = (m[j * 3 + i] + m[i * 3 + j]) * t; v[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
-    q.x = v[0]; q.y = v[1]; q.z = v[2];
-    return q;
-}
-HQ h_qn(HQ a) { const double n = std::sqrt(a.w * a.w + a.x * a.x + a.y * a.y + a.z * a.z); return HQ{a.w / n, a.x / n, a.y / n, a.z / n}; }
-HQ h_qinv(HQ a) { const double n2 = a.w * a.w + a.x * a.x + a.y * a.y + a.z * a.z; return HQ{a.w / n2, -a.x / n2, -a.y / n2, -a.z / n2}; }
-HQ h_qmul(HQ a, HQ b) { return HQ{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z, a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x}; }
-void h_mm(const double *A, const double *B, double *C) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double s = 0; for (int k = 0; k < 3; k++) s += A[i * 3 + k] * B[k * 3 + j]; C[i * 3 + j] = s; } }
-void h_mv(const double *A, const double *v, double *o) { for (int i = 0; i < 3; i++) o[i] = A[i * 3] * v[0] + A[i * 3 + 1] * v[1] + A[i * 3 + 2] * v[2]; }
-void h_mtv(const double *A, const double *v, double *o) { for (int i = 0; i < 3; i++) o[i] = A[i] * v[0] + A[3 + i] * v[1] + A[6 + i] * v[2]; }
-void h_log(HQ q, double *om) {   // Sophus SO3::log of a unit quaternion
-    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z, n = std::sqrt(n2);
-    double f;
-    if (n2 < 1e-20) f = 2.0 / q.w - 2.0 / 3.0 * n2 / (q.w * q.w * q.w);
-    else if (std::fabs(q.w) < 1e-10) f = (q.w > 0 ? M_PI : -M_PI) / n;
-    else f = 2.0 * std::atan(n / q.w) / n;
-    om[0] = f * q.x; om[1] = f * q.y; om[2] = f * q.z;
-}
-HQ h_exp(const double *om) {
-    const double t2 = om[0] * om[0] + om[1] * om[1] + om[2] * om[2], t = std::sqrt(t2);
-    double im, re;
-    if (t2 < 1e-20) { const double t4 = t2 * t2; im = 0.5 - t2 / 48.0 + t4 / 3840.0; re = 1.0 - t2 / 8.0 + t4 / 384.0; }
-    else { im = std::sin(0.5 * t) / t; re = std::cos(0.5 * t); }
-    return HQ{re, im * om[0], im * om[1], im * om[2]};
-}
-void h_R2ypr(const double *R, double *ypr) {     // Utility::R2ypr, degrees
-    const double y = std::atan2(R[3], R[0]), p = std::atan2(-R[6], R[0] * std::cos(y) + R[3] * std::sin(y));
-    const double r = std::atan2(R[2] * std::sin(y) - R[5] * std::cos(y), -R[1] * std::sin(y) + R[4] * std::cos(y));
-    ypr[0] = y / M_PI * 180.0; ypr[1] = p / M_PI * 180.0; ypr[2] = r / M_PI * 180.0;
-}
-// RelativePoseFactor::update, solver overload (include/factor/relative_pose_factor.h:103-117)
-void h_relpose_update(isv_relpose_t *f, const double *ti, const double *Ri, const double *tj, const double *Rj, const double *PSi, const double *PSj) {
-    const HQ Qi{PSi[6], PSi[3], PSi[4], PSi[5]}, Qj{PSj[6], PSj[3], PSj[4], PSj[5]};
-    double d_tj[3], d_ti[3], Qm[9], A[9], B[9], lgi[3], lgj[3], v1[3], v2[3];
-    for (int k = 0; k < 3; k++) { d_tj[k] = PSj[k] - tj[k]; d_ti[k] = PSi[k] - ti[k]; }
-    h_q2R(h_qinv(Qj), Qm); h_mm(Qm, Rj, A); h_log(h_qn(h_R2q(A)), lgj);
-    h_q2R(h_qinv(Qi), Qm); h_mm(Qm, Ri, B); h_log(h_qn(h_R2q(B)), lgi);
-    h_mtv(Ri, d_tj, v1); h_mtv(Ri, d_ti, v2);
-    const double *t = f->delta_t;
-    const double v3[3] = {t[1] * lgi[2] - t[2] * lgi[1], t[2] * lgi[0] - t[0] * lgi[2], t[0] * lgi[1] - t[1] * lgi[0]};     // skew(delta_t) * log
-    for (int k = 0; k < 3; k++) f->delta_t[k] += v1[k] - v2[k] + v3[k];
-    double Ji[9], w[3], E[9], T[9];
-    h_q2R(h_qmul(h_qinv(Qj), Qi), Ji);
-    for (int k = 0; k < 9; k++) Ji[k] = -Ji[k];
-    h_mv(Ji, lgi, w);
-    h_q2R(h_exp(w), E); h_mm(f->delta_R, E, T); memcpy(f->delta_R, T, sizeof(T));
-    h_q2R(h_exp(lgj), E); h_mm(f->delta_R, E, T); memcpy(f->delta_R, T, sizeof(T));
-}
-void h_inv6(const double *Ain, double *Inv) {    // PartialPivLU inverse of a 6x6 (Eigen MatrixXd::inverse)
-    double A[36]; memcpy(A, Ain, sizeof(A));
-    int perm[6]; for (int i = 0; i < 6; i++) perm[i] = i;
-    for (int k = 0; k < 6; k++) {
-        int p = k; double best = std::fabs(A[k * 6 + k]);
-        for (int i = k + 1; i < 6; i++) if (std::fabs(A[i * 6 + k]) > best) { best = std::fabs(A[i * 6 + k]); p = i; }
-        if (p != k) { for (int j = 0; j < 6; j++) std::swap(A[k * 6 + j], A[p * 6 + j]); std::swap(perm[k], perm[p]); }
-        for (int i = k + 1; i < 6; i++) { A[i * 6 + k] /= A[k * 6 + k]; for (int j = k + 1; j < 6; j++) A[i * 6 + j] -= A[i * 6 + k] * A[k * 6 + j]; }
-    }
-    for (int c = 0; c < 6; c++) {
-        double x[6];
-        for (int i = 0; i < 6; i++) x[i] = perm[i] == c ? 1.0 : 0.0;
-        for (int i = 0; i < 6; i++) { double s = x[i]; for (int k = 0; k < i; k++) s -= A[i * 6 + k] * x[k]; x[i] = s; }
-        for (int i = 5; i >= 0; i--) { double s = x[i]; for (int k = i + 1; k < 6; k++) s -= A[i * 6 + k] * x[k]; x[i] = s / A[i * 6 + i]; }
-        for (int i = 0; i < 6; i++) Inv[i * 6 + c] = x[i];
-    }
-}
-}  // namespace
 
 // CombinedFactors::operator+ (include/factor/pose_graph_factors.h:27-51); host arithmetic on 6x6 matrices
 extern "C" int isv_combined_factors_add(isv_combined_factors_t *acc, int32_t *acc_length, int64_t *acc_vio_index,
@@ -1055,403 +939,119 @@ extern "C" int isv_combined_factors_add(isv_combined_factors_t *acc, int32_t *ac
     return ISV_OK;
 }
 
+// ---- the HIP side of a call -------------------------------------------------------------------------------------------
+// step 4: the batch's arrays live in ONE pinned staging area kept with the handle (no zero-initialised vectors per call, and the
+// copies to and from the device run at the pinned rate); it grows by a quarter more than is needed
+static int pgo_stage(isv_pgo *h, PgCall &call) {
+    const size_t need = call.sec_off[PGA_COUNT];
+    if (need > h->pin_cap) {
+        if (h->pin) (void)hipHostFree(h->pin);
+        h->pin = nullptr; h->pin_cap = 0;
+        PCHK(h, hipHostMalloc(&h->pin, need + need / 4, hipHostMallocDefault));
+        h->pin_cap = need + need / 4;
+    }
+    pg_carve(call, h->pin);
+    return ISV_OK;
+}
+
+// chunk c's range of every array of direction `dir` on the chunk's stream: staging -> device (PG_UP) or back (PG_DOWN)
+static hipError_t pgo_copy_chunk(isv_pgo *h, const PgCall &call, int c, unsigned dir) {
+    const auto &lo = call.off[call.chunk_lo(c)], &hi = call.off[call.chunk_lo(c + 1)];
+    hipError_t e = hipSuccess;
+    pg_for_each_array(call, h->d, PG_NO_GRAPH, [&](int a, unsigned role, auto *sp, auto *dp, size_t, const auto *) {
+        if (!(role & dir) || hi[a] <= lo[a] || e != hipSuccess) return;
+        const size_t bytes = sizeof(*sp) * (hi[a] - lo[a]);
+        e = dir == PG_UP ? hipMemcpyAsync(dp + lo[a], sp + lo[a], bytes, hipMemcpyHostToDevice, h->cstream[c])
+                         : hipMemcpyAsync(sp + lo[a], dp + lo[a], bytes, hipMemcpyDeviceToHost, h->cstream[c]);
+    });
+    return e;
+}
+
+// [uploads -> k_pgo between the chunk's two events -> results into the staging] on the chunk's stream
+// (round 5) a call that leaves CUs idle gives every graph four wavefronts -- the same bits (k_pgo's header); ISV_PGO_WAVES=1 / 4 forces a form
+static int pgo_enqueue_chunk(isv_pgo *h, const PgCall &call, int c, bool waves4, std::atomic<int> &first_chunk, std::string &msg) {
+    const int g0 = call.chunk_lo(c), g1 = call.chunk_lo(c + 1);
+    hipStream_t st = h->cstream[c];
+    PMSG(msg, hipSetDevice(h->device));
+    PMSG(msg, hipMemcpyAsync(h->d.graphs + g0, call.graphs.data() + g0, sizeof(PgGraph) * (size_t)(g1 - g0), hipMemcpyHostToDevice, st));     // (pageable, 80 B per graph)
+    PMSG(msg, pgo_copy_chunk(h, call, c, PG_UP));
+    PgDev dv = h->d; dv.g0 = g0;
+    PMSG(msg, hipEventRecord(h->kev[c][0], st));
+    if (waves4) hipLaunchKernelGGL(k_pgo<4>, dim3(g1 - g0), dim3(256), call.idx_bytes, st, dv);
+    else hipLaunchKernelGGL(k_pgo<1>, dim3(g1 - g0), dim3(64), call.idx_bytes, st, dv);
+    PMSG(msg, hipGetLastError());
+    PMSG(msg, hipEventRecord(h->kev[c][1], st));
+    PMSG(msg, pgo_copy_chunk(h, call, c, PG_DOWN));
+    int exp = -1; first_chunk.compare_exchange_strong(exp, c);
+    return ISV_OK;
+}
+
+static int pgo_drain_chunk(isv_pgo *h, const PgCall &call, int c, std::string &msg) {
+    const hipError_t e1 = hipSetDevice(h->device), e2 = e1 == hipSuccess ? hipStreamSynchronize(h->cstream[c]) : e1;
+    if (e2 != hipSuccess) { msg = std::string("hipStreamSynchronize: ") + hipGetErrorString(e2); return ISV_ERR_DEVICE; }
+    pg_publish_results(call, c);
+    return ISV_OK;
+}
+
+// step 6: the span of the chunks' kernels (the chunk enqueued first, fc, starts first), and the ISV_TRACE_HANDOVER lines
+static void pgo_kernel_time(isv_pgo *h, int C, int fc) {
+    float best = 0;
+    for (int c = 0; c < C; c++) { float f = 0; if (hipEventElapsedTime(&f, h->kev[fc][0], h->kev[c][1]) == hipSuccess) best = std::max(best, f); else (void)hipGetLastError(); }
+    h->last_kernel_ms = best;
+}
+static void pgo_trace(isv_pgo *h, const PgCall &call, const PgPipeTimes &tm, int fc, std::chrono::steady_clock::time_point tp0, std::chrono::steady_clock::time_point tp1) {
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto tp2 = tm.enq[call.C - 1], tp3 = tm.done[call.C - 1];      // the last chunk's enqueue, the last chunk's drain
+    fprintf(stderr, "isv pgo batch: %d graphs: analysis %.2f ms, assembly %.2f ms, H2D + kernel + D2H %.2f ms (%.1f MB up), write-back %.2f ms\n", call.ng, ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3),
+            pg_upload_bytes(call, h->d) / 1e6, ms(tp3, std::chrono::steady_clock::now()));
+    for (int c = 0; c < call.C; c++) {       // every chunk's kernel on the first chunk's clock, and when the host enqueued / found it drained
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, h->kev[fc][0], h->kev[c][0]); (void)hipEventElapsedTime(&b, h->kev[fc][0], h->kev[c][1]); (void)hipGetLastError();
+        fprintf(stderr, "  chunk %d: graphs [%d, %d): enqueued at %.2f ms, k_pgo %.2f .. %.2f ms after the first chunk's start, drained at %.2f ms\n", c, call.chunk_lo(c), call.chunk_lo(c + 1),
+                ms(tp0, tm.enq[c]), a, b, ms(tp0, tm.done[c]));
+    }
+}
+
 extern "C" int isv_pgo_optimize_batch(isv_pgo_t *h, int32_t ng, const int32_t *ns, isv_pg_keyframe_t *const *kfs, const int32_t *firsts,
                                       const int32_t *curs, isv_pgo_result_t *results) {
+    // 1. the arguments
     if (!h || ng < 1 || !ns || !kfs || !firsts || !curs || !results) return ISV_ERR_INVALID_ARG;
     PCHK(h, hipSetDevice(h->device));
     if (ng > h->cfg.max_graphs) { h->err = "more graphs than max_graphs"; return ISV_ERR_CAPACITY; }
-    // host preparation: the graphs are analysed independently (parameter blocks, residual blocks, skyline, column patterns) into
-    // per-graph buffers by min(8, cores, graphs) host threads (ISV_HOST_THREADS overrides), then laid end to end
-    struct GraphBuild {
-        std::vector<double> pose; std::vector<int32_t> free_of, adj_ptr, adj, start, rowptr, colptr, colrows; std::vector<PgEdge> edges; std::vector<uint64_t> raw_key;
-        const char *err = nullptr; int rc = ISV_OK;
-    };
-    std::vector<PgGraph> graphs(ng);
-    std::vector<GraphBuild> builds(ng);
-    std::vector<std::vector<int>> local(ng);
-    std::vector<int> cur_pos(ng, -1), n_loops(ng, 0);
     if (h->cache.size() < (size_t)h->cfg.max_graphs) h->cache.resize((size_t)h->cfg.max_graphs);
     static const bool no_cache = getenv("ISV_PGO_NO_CACHE") != nullptr;       // (A/B and test hook; PROCESS-wide: read once, at the first call)
-    std::vector<char> hit(ng, 0);
-    auto fill_edge_numbers = [&](PgEdge &E, const isv_pg_keyframe_t &k) {
-        if (E.kind == 0) { memcpy(E.meas_R, k.rollpitch.R, 72); memcpy(E.sqrt_info, k.rollpitch.sqrt_info, 32); }
-        else if (E.kind == 1) { memcpy(E.meas_t, k.relative_pose.delta_t, 24); memcpy(E.meas_R, k.relative_pose.delta_R, 72); memcpy(E.sqrt_info, k.relative_pose.sqrt_info, 288); }
-        else {
-            memcpy(E.meas_t, k.loop_info, 24);
-            h_q2R(HQ{k.loop_info[3], k.loop_info[4], k.loop_info[5], k.loop_info[6]}, E.meas_R);
-            for (int dd = 0; dd < 6; dd++) E.sqrt_info[dd * 6 + dd] = std::sqrt(k.loop_weight);
-        }
-    };
-    auto build_graph = [&](int g) -> int {
-        const int n = ns[g]; isv_pg_keyframe_t *kf = kfs[g];
-        if (n < 1 || !kf) return ISV_ERR_INVALID_ARG;
-        PgGraph &G = graphs[g];
-        memset(&G, 0, sizeof(G));
-        GraphBuild &B = builds[g];
-        // ---- the cached structure of this slot, when nothing it depends on has changed ----
-        PgStructCache &SC = h->cache[g];
-        uint64_t key = 1469598103934665603ull;
-        std::vector<uint64_t> &raw = B.raw_key;
-        raw.clear(); raw.reserve(3 + 2 * (size_t)n);
-        auto mix = [&](uint64_t v) { raw.push_back(v); key ^= v + 0x9e3779b97f4a7c15ull + (key << 6) + (key >> 2); };
-        mix((uint64_t)n); mix((uint64_t)(uint32_t)firsts[g]); mix((uint64_t)(uint32_t)curs[g]);
-        for (int k = 0; k < n; k++) {
-            mix(((uint64_t)(uint32_t)kf[k].index << 32) | (uint32_t)kf[k].sequence);
-            mix(((uint64_t)(kf[k].has_rollpitch != 0) << 33) | ((uint64_t)(kf[k].has_loop != 0) << 32) | (uint32_t)(kf[k].has_loop ? kf[k].loop_index : 0));
-        }
-        // (the hash only short-cuts the comparison: the tuple itself decides)
-        if (!no_cache && SC.valid && SC.key == key && (int)SC.loc.size() == n && SC.raw.size() == raw.size() && memcmp(SC.raw.data(), raw.data(), raw.size() * sizeof(uint64_t)) == 0) {
-            G.max_iter = h->cfg.max_iterations; G.huber = h->cfg.huber_delta;
-            G.P1 = SC.P1; G.nf = SC.nf; G.nblk = SC.nblk; G.ne = (int32_t)SC.edges.size();
-            local[g] = SC.loc; cur_pos[g] = SC.cur_pos; n_loops[g] = SC.n_loops;
-            B.pose.reserve((size_t)SC.P1 * 7);
-            for (int k = 0; k < n; k++) {
-                if (SC.loc[k] < 0) continue;
-                for (int c = 0; c < 9; c++) if (!(kf[k].vio_R_w_i[c] - kf[k].vio_R_w_i[c] == 0.0)) { B.err = "non-finite keyframe pose"; return ISV_ERR_NONFINITE; }
-                const HQ q = h_qn(h_R2q(kf[k].vio_R_w_i));
-                B.pose.insert(B.pose.end(), {kf[k].vio_T_w_i[0], kf[k].vio_T_w_i[1], kf[k].vio_T_w_i[2], q.x, q.y, q.z, q.w});
-            }
-            B.free_of = SC.free_of; B.adj_ptr = SC.adj_ptr; B.adj = SC.adj; B.start = SC.start; B.rowptr = SC.rowptr; B.colptr = SC.colptr; B.colrows = SC.colrows;
-            B.edges.resize(SC.edges.size());
-            for (size_t e = 0; e < SC.edges.size(); e++) {
-                const PgEdgeTpl &T = SC.edges[e];
-                PgEdge &E = B.edges[e];
-                memset(&E, 0, sizeof(E));
-                E.kind = T.kind; E.a = T.a; E.b = T.b; E.fa = T.fa; E.fb = T.fb; E.dim = T.dim; E.robust = T.robust;
-                fill_edge_numbers(E, kf[T.src]);
-            }
-            hit[g] = 1;
-            return ISV_OK;
-        }
-        SC.valid = false;
-        std::vector<int32_t> edge_src;
-        std::vector<double> &pose = B.pose; std::vector<int32_t> &free_of = B.free_of, &adj_ptr = B.adj_ptr, &adj = B.adj, &start = B.start, &rowptr = B.rowptr, &colptr = B.colptr, &colrows = B.colrows;
-        std::vector<PgEdge> &edges = B.edges;
-        G.max_iter = h->cfg.max_iterations; G.huber = h->cfg.huber_delta;
-        // parameter blocks: keyframes first_looped_index .. cur_index in list order (pose_graph.cpp:277-306)
-        std::vector<int> &loc = local[g];
-        loc.assign(n, -1);
-        int pi = 0;
-        for (int k = 0; k < n; k++) {
-            if (kf[k].index < firsts[g] || cur_pos[g] >= 0) continue;
-            loc[k] = pi++;
-            if (kf[k].index == curs[g]) cur_pos[g] = k;
-        }
-        if (cur_pos[g] < 0) { B.err = "cur_index is not in the keyframe list (or lies before first_looped_index)"; return ISV_ERR_INVALID_ARG; }
-        if (pi > h->cfg.max_keyframes) { B.err = "more keyframes than max_keyframes"; return ISV_ERR_CAPACITY; }
-        G.P1 = pi;
-        const int param_index = pi - 1;
-        std::vector<int> fo(pi, -1);
-        int nf = 0;
-        for (int k = 0; k < n; k++) {
-            const int li = loc[k]; if (li < 0) continue;
-            for (int c = 0; c < 9; c++) if (!(kf[k].vio_R_w_i[c] - kf[k].vio_R_w_i[c] == 0.0)) { B.err = "non-finite keyframe pose"; return ISV_ERR_NONFINITE; }
-            const HQ q = h_qn(h_R2q(kf[k].vio_R_w_i));                    // tmp_q = tmp_r; tmp_q.normalize()
-            pose.insert(pose.end(), {kf[k].vio_T_w_i[0], kf[k].vio_T_w_i[1], kf[k].vio_T_w_i[2], q.x, q.y, q.z, q.w});
-            const bool constant = kf[k].index == firsts[g] || kf[k].sequence == 0;
-            fo[li] = constant ? -1 : nf++;
-        }
-        G.nf = nf;
-        free_of.insert(free_of.end(), fo.begin(), fo.end());
-        // residual blocks of the keyframes BEFORE cur (pose_graph.cpp:309-339)
-        std::vector<std::vector<int32_t>> adjl(nf);
-        std::vector<int> st(nf);
-        for (int f = 0; f < nf; f++) st[f] = f;
-        auto add_edge = [&](PgEdge &E) {
-            E.fa = fo[E.a]; E.fb = E.kind == 0 ? -1 : fo[E.b];
-            const int id = (int)edges.size();
-            if (E.fa >= 0) adjl[E.fa].push_back((id << 1) | 0);
-            if (E.kind != 0 && E.fb >= 0) adjl[E.fb].push_back((id << 1) | 1);
-            if (E.kind != 0 && E.fa >= 0 && E.fb >= 0) { const int lo = std::min(E.fa, E.fb), hi = std::max(E.fa, E.fb); st[hi] = std::min(st[hi], lo); }
-            edges.push_back(E);
-        };
-        for (int k = 0; k < n; k++) {
-            const int li = loc[k]; if (li < 0 || k == cur_pos[g]) continue;
-            if (kf[k].has_rollpitch) {
-                PgEdge E; memset(&E, 0, sizeof(E));
-                E.kind = 0; E.a = E.b = li; E.dim = 2;
-                memcpy(E.meas_R, kf[k].rollpitch.R, 72); memcpy(E.sqrt_info, kf[k].rollpitch.sqrt_info, 32);
-                add_edge(E); edge_src.push_back(k);
-            }
-            if (li + 1 <= param_index) {
-                PgEdge E; memset(&E, 0, sizeof(E));
-                E.kind = 1; E.a = li; E.b = li + 1; E.dim = 6;
-                memcpy(E.meas_t, kf[k].relative_pose.delta_t, 24); memcpy(E.meas_R, kf[k].relative_pose.delta_R, 72); memcpy(E.sqrt_info, kf[k].relative_pose.sqrt_info, 288);
-                add_edge(E); edge_src.push_back(k);
-            }
-            if (kf[k].has_loop) {
-                int conn = -1;
-                for (int m = 0; m < n; m++) if (kf[m].index == kf[k].loop_index) conn = loc[m];
-                if (conn < 0) { B.err = "loop_index outside the optimised range (the reference asserts loop_index >= first_looped_index)"; return ISV_ERR_INVALID_ARG; }
-                PgEdge E; memset(&E, 0, sizeof(E));
-                E.kind = 2; E.a = conn; E.b = li; E.dim = 6; E.robust = 1;
-                memcpy(E.meas_t, kf[k].loop_info, 24);
-                h_q2R(HQ{kf[k].loop_info[3], kf[k].loop_info[4], kf[k].loop_info[5], kf[k].loop_info[6]}, E.meas_R);
-                for (int dd = 0; dd < 6; dd++) E.sqrt_info[dd * 6 + dd] = std::sqrt(kf[k].loop_weight);
-                add_edge(E); edge_src.push_back(k);
-                n_loops[g]++;
-            }
-        }
-        G.ne = (int32_t)edges.size();
-        // skyline + adjacency + column patterns
-        int nb = 0;
-        for (int f = 0; f < nf; f++) { adj_ptr.push_back((int32_t)adj.size()); adj.insert(adj.end(), adjl[f].begin(), adjl[f].end()); start.push_back(st[f]); rowptr.push_back(nb); nb += f - st[f] + 1; }
-        adj_ptr.push_back((int32_t)adj.size()); rowptr.push_back(nb);
-        G.nblk = nb;
-        if (nb - 2 * nf > h->cfg.max_loop_blocks) { B.err = "loop closures span more blocks than max_loop_blocks"; return ISV_ERR_CAPACITY; }
-        std::vector<std::vector<int32_t>> cp(nf);
-        for (int i = 0; i < nf; i++) for (int j = st[i]; j < i; j++) cp[j].push_back(i);
-        for (int j = 0; j < nf; j++) { colptr.push_back((int32_t)colrows.size()); colrows.insert(colrows.end(), cp[j].begin(), cp[j].end()); }
-        colptr.push_back((int32_t)colrows.size());
-        // remember the structure for the next call on this slot
-        SC.key = key; SC.raw = raw; SC.loc = loc; SC.cur_pos = cur_pos[g]; SC.n_loops = n_loops[g]; SC.P1 = G.P1; SC.nf = G.nf; SC.nblk = G.nblk;
-        SC.free_of = free_of; SC.adj_ptr = adj_ptr; SC.adj = adj; SC.start = start; SC.rowptr = rowptr; SC.colptr = colptr; SC.colrows = colrows;
-        SC.edges.resize(edges.size());
-        for (size_t e = 0; e < edges.size(); e++) SC.edges[e] = PgEdgeTpl{edges[e].kind, edges[e].a, edges[e].b, edges[e].fa, edges[e].fb, edges[e].dim, edges[e].robust, edge_src[e]};
-        SC.valid = true;
-        return ISV_OK;
-    };
-    auto parallel_over_graphs = [&](const std::function<void(int)> &fn) {
-        int T = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-        if (const char *ev = getenv("ISV_HOST_THREADS")) T = atoi(ev);
-        T = std::max(1, std::min(T, ng));
-        if (T == 1) { for (int g = 0; g < ng; g++) fn(g); return; }
-        std::atomic<int> next{0};
-        std::vector<std::thread> th;
-        for (int k = 0; k < T; k++) th.emplace_back([&] { for (int g; (g = next.fetch_add(1)) < ng; ) fn(g); });
-        for (auto &x : th) x.join();
-    };
+    PgCall call;
+    call.ng = ng; call.ns = ns; call.kfs = kfs; call.firsts = firsts; call.curs = curs; call.results = results; call.slots = h->cache.data();
+    call.T = pg_host_threads(ng); call.C = pg_chunk_count(ng);
+    // 2. structure (the slot's, or analysed into it) and numbers of every graph, on the team
     const auto tp0 = std::chrono::steady_clock::now();
-    parallel_over_graphs([&](int g) { builds[g].rc = build_graph(g); });
+    int64_t hits = 0;
+    PTRY(pg_prepare_batch(call, h->cfg, no_cache, h->err, &hits));
     const auto tp1 = std::chrono::steady_clock::now();
-    for (int g = 0; g < ng; g++) if (builds[g].rc != ISV_OK) { if (builds[g].err) h->err = builds[g].err; return builds[g].rc; }
-    for (int g = 0; g < ng; g++) h->cache_hits += hit[g];
-    // the batch's arrays live in ONE pinned staging area kept with the handle: no zero-initialised 170 MB vectors per call
-    // (a third of a 1024-graph call in round 2), and the copies to and from the device run at the pinned rate
-    struct SpanD { double *p = nullptr; size_t n = 0; double *data() const { return p; } size_t size() const { return n; } bool empty() const { return n == 0; } double &operator[](size_t i) const { return p[i]; } };
-    struct SpanI { int32_t *p = nullptr; size_t n = 0; int32_t *data() const { return p; } size_t size() const { return n; } bool empty() const { return n == 0; } int32_t &operator[](size_t i) const { return p[i]; } };
-    struct SpanE { PgEdge *p = nullptr; size_t n = 0; PgEdge *data() const { return p; } size_t size() const { return n; } bool empty() const { return n == 0; } PgEdge &operator[](size_t i) const { return p[i]; } };
-    SpanD pose; SpanI free_of, adj_ptr, adj, start, rowptr, colptr, colrows; SpanE edges;
-    size_t nblk_tot = 0, nfree_tot = 0;
-    // offsets first (serial, integers only), then the per-graph buffers are copied into place by the host threads: the serial
-    // append of round 2 moved ~240 KB per graph (the edge records) on ONE thread, half of a 1024-graph call
-    struct Off { size_t pose, free_of, adj_ptr, adj, start, rowptr, colptr, colrows, edges; };
-    std::vector<Off> off((size_t)ng + 1);
-    memset(&off[0], 0, sizeof(Off));
-    for (int g = 0; g < ng; g++) {
-        PgGraph &G = graphs[g]; const GraphBuild &B = builds[g]; const Off &o = off[g];
-        G.pose0 = (int32_t)(o.pose / 7); G.free0 = (int32_t)nfree_tot; G.edge0 = (int32_t)o.edges; G.blk0 = (int32_t)nblk_tot;
-        G.adj0 = (int32_t)o.adj; G.col0 = (int32_t)o.colrows; G.vec0 = (int32_t)(6 * nfree_tot);
-        off[g + 1] = Off{o.pose + B.pose.size(), o.free_of + B.free_of.size(), o.adj_ptr + B.adj_ptr.size(), o.adj + B.adj.size(), o.start + B.start.size(),
-                         o.rowptr + B.rowptr.size(), o.colptr + B.colptr.size(), o.colrows + B.colrows.size(), o.edges + B.edges.size()};
-        nblk_tot += (size_t)G.nblk; nfree_tot += (size_t)G.nf;
+    h->cache_hits += hits;
+    // 3. + 4. the graphs laid end to end, the staging grown and carved
+    PTRY(pg_layout(call, h->d, h->cfg, h->cap, getenv("ISV_PGO_IDX_GLOBAL") != nullptr, h->err));
+    PTRY(pgo_stage(h, call));
+    h->d.idx_lds_rows = call.idx_lds_rows; h->d.idx_lds_cols = call.idx_lds_cols;
+    h->last_blocks = (double)call.nblk_tot;
+    // 5. the chunk pipeline
+    bool waves4 = ng <= h->n_cus;
+    if (const char *ev = getenv("ISV_PGO_WAVES")) waves4 = atoi(ev) > 1;
+    std::atomic<int> first_chunk{-1};
+    PgPipeTimes tm;
+    const int rc = pg_run_pipeline(call, tm, h->err, [&](int g) { pg_assemble(call, h->d, g); },
+                                   [&](int c, std::string &msg) { return pgo_enqueue_chunk(h, call, c, waves4, first_chunk, msg); },
+                                   [&](int c, std::string &msg) { return pgo_drain_chunk(h, call, c, msg); }, [&](int g) { pg_write_back(call, g); });
+    if (rc != ISV_OK) {
+        for (int c = 0; c < call.C; c++) (void)hipStreamSynchronize(h->cstream[c]);      // nothing of this call stays in flight
+        return rc;
     }
-    SpanD cov;
-    isv_pgo_result_t *res_stage = nullptr;
-    {
-        const Off &e = off[ng];
-        auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
-        const size_t b_pose = al(e.pose * 8), b_cov = al(e.pose / 7 * 36 * 8), b_edges = al(e.edges * sizeof(PgEdge)), b_res = al((size_t)ng * sizeof(isv_pgo_result_t));
-        const size_t b_i[7] = {al(e.free_of * 4), al(e.adj_ptr * 4), al(e.adj * 4), al(e.start * 4), al(e.rowptr * 4), al(e.colptr * 4), al(e.colrows * 4)};
-        size_t need = b_pose + b_cov + b_edges + b_res;
-        for (size_t b : b_i) need += b;
-        if (need > h->pin_cap) {
-            if (h->pin) (void)hipHostFree(h->pin);
-            h->pin = nullptr; h->pin_cap = 0;
-            PCHK(h, hipHostMalloc(&h->pin, need + need / 4, hipHostMallocDefault));
-            h->pin_cap = need + need / 4;
-        }
-        char *q = (char *)h->pin;
-        pose.p = (double *)q; pose.n = e.pose; q += b_pose;
-        cov.p = (double *)q; cov.n = e.pose / 7 * 36; q += b_cov;
-        edges.p = (PgEdge *)q; edges.n = e.edges; q += b_edges;
-        res_stage = (isv_pgo_result_t *)q; q += b_res;
-        SpanI *si[7] = {&free_of, &adj_ptr, &adj, &start, &rowptr, &colptr, &colrows};
-        const size_t ni[7] = {e.free_of, e.adj_ptr, e.adj, e.start, e.rowptr, e.colptr, e.colrows};
-        for (int k = 0; k < 7; k++) { si[k]->p = (int32_t *)q; si[k]->n = ni[k]; q += b_i[k]; }
-    }
-    {
-        const Off &e = off[ng];
-        if (e.pose / 7 > h->cap_pose || e.edges > h->cap_edge || nblk_tot > h->cap_blk || e.adj > h->cap_adj || e.colrows > h->cap_col) {
-            h->err = "pose graphs exceed the handle's capacity"; return ISV_ERR_CAPACITY;
-        }
-    }
-    PgDev &d = h->d;
-    // index arrays of the envelope in LDS when the largest graph's fit into 48 KB
-    size_t max_nf = 0, max_cols = 0;
-    for (int g = 0; g < ng; g++) {
-        max_nf = std::max(max_nf, (size_t)graphs[g].nf);
-        max_cols = std::max(max_cols, (size_t)(graphs[g].nblk - graphs[g].nf));
-    }
-    size_t idx_bytes = (3 * max_nf + 1 + max_cols) * sizeof(int32_t);
-    d.idx_lds_rows = d.idx_lds_cols = 0;
-    // (ISV_PGO_IDX_GLOBAL: test hook for the path graphs too large for the LDS copies take)
-    if (max_nf > 0 && idx_bytes <= 48 * 1024 && !getenv("ISV_PGO_IDX_GLOBAL")) { d.idx_lds_rows = (int32_t)max_nf; d.idx_lds_cols = (int32_t)max_cols; } else idx_bytes = 0;
-    h->last_blocks = (double)nblk_tot;
-    // ---- the chunked pipeline: [assemble chunk c into the pinned staging -> H2D -> k_pgo -> D2H] on stream c, then write-back ----
-    // One team of host threads walks 2 ng tasks in order (an atomic counter): task g < ng copies graph g's arrays into place, the
-    // thread that completes a chunk's last graph enqueues the chunk; task ng + g writes graph g back, after the chunk's stream has
-    // drained (the first thread to get there waits for it).  Chunks are contiguous graph ranges, so every array of a chunk is ONE
-    // range of the batch's arrays and the offsets the kernel uses are the batch's.
-    int C = ng >= 64 ? isv_pgo::PG_CHUNKS : 1;
-    if (const char *ev = getenv("ISV_PGO_CHUNKS")) { C = atoi(ev); if (C < 1) C = 1; if (C > isv_pgo::PG_CHUNKS) C = isv_pgo::PG_CHUNKS; if (C > ng) C = ng; }
-    auto chunk_lo = [&](int c) { return (int)((int64_t)ng * c / C); };
-    auto chunk_of = [&](int g) { int c = (int)(((int64_t)g * C) / ng); while (c + 1 < C && g >= chunk_lo(c + 1)) c++; while (c > 0 && g < chunk_lo(c)) c--; return c; };
-    std::vector<std::atomic<int>> left((size_t)C), enq((size_t)C), done((size_t)C);
-    for (int c = 0; c < C; c++) { left[c].store(chunk_lo(c + 1) - chunk_lo(c)); enq[c].store(0); done[c].store(0); }
-    std::atomic<int> first_chunk{-1}, fail_rc{ISV_OK};
-    std::mutex err_mu, done_mu[isv_pgo::PG_CHUNKS];
-    auto fail = [&](int rc, const std::string &msg) { std::lock_guard<std::mutex> lk(err_mu); if (fail_rc.load() == ISV_OK) { fail_rc.store(rc); h->err = msg; } };
-#define TCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(ISV_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); return; } } while (0)
-    bool pgo_waves4 = ng <= h->n_cus;
-    if (const char *ev = getenv("ISV_PGO_WAVES")) pgo_waves4 = atoi(ev) > 1;
-    auto enqueue_chunk = [&](int c) {
-        const int g0 = chunk_lo(c), g1 = chunk_lo(c + 1);
-        const Off &a = off[g0], &b = off[g1];
-        hipStream_t st = h->cstream[c];
-        TCHK(hipSetDevice(h->device));
-#define UPR(dst, src, lo, hi) do { if ((hi) > (lo)) TCHK(hipMemcpyAsync((dst) + (lo), (src).data() + (lo), sizeof((src)[0]) * ((hi) - (lo)), hipMemcpyHostToDevice, st)); } while (0)
-        TCHK(hipMemcpyAsync(d.graphs + g0, graphs.data() + g0, sizeof(PgGraph) * (size_t)(g1 - g0), hipMemcpyHostToDevice, st));     // (pageable, 80 B per graph)
-        UPR(d.pose, pose, a.pose, b.pose); UPR(d.free_of, free_of, a.free_of, b.free_of); UPR(d.edges, edges, a.edges, b.edges);
-        UPR(d.adj_ptr, adj_ptr, a.adj_ptr, b.adj_ptr); UPR(d.adj, adj, a.adj, b.adj); UPR(d.start, start, a.start, b.start);
-        UPR(d.rowptr, rowptr, a.rowptr, b.rowptr); UPR(d.colptr, colptr, a.colptr, b.colptr); UPR(d.colrows, colrows, a.colrows, b.colrows);
-#undef UPR
-        PgDev dv = d; dv.g0 = g0;
-        TCHK(hipEventRecord(h->kev[c][0], st));
-        // (round 5) a call that leaves CUs idle gives every graph four wavefronts -- the same bits (k_pgo's header); ISV_PGO_WAVES=1 / 4 forces a form
-        if (pgo_waves4) hipLaunchKernelGGL(k_pgo<4>, dim3(g1 - g0), dim3(256), idx_bytes, st, dv);
-        else hipLaunchKernelGGL(k_pgo<1>, dim3(g1 - g0), dim3(64), idx_bytes, st, dv);
-        TCHK(hipGetLastError());
-        TCHK(hipEventRecord(h->kev[c][1], st));
-        // results into the pinned staging (the caller's arrays are pageable: copied from there after the stream has drained)
-        if (b.pose > a.pose) {
-            TCHK(hipMemcpyAsync(pose.data() + a.pose, d.pose + a.pose, sizeof(double) * (b.pose - a.pose), hipMemcpyDeviceToHost, st));
-            TCHK(hipMemcpyAsync(cov.data() + a.pose / 7 * 36, d.cov + a.pose / 7 * 36, sizeof(double) * (b.pose - a.pose) / 7 * 36, hipMemcpyDeviceToHost, st));
-        }
-        TCHK(hipMemcpyAsync(res_stage + g0, d.res + g0, sizeof(isv_pgo_result_t) * (size_t)(g1 - g0), hipMemcpyDeviceToHost, st));
-        int exp = -1; first_chunk.compare_exchange_strong(exp, c);
-    };
-    auto assemble = [&](int g) {
-        GraphBuild &B = builds[g]; const Off &o = off[g];
-#define PUT(v) do { if (!B.v.empty()) memcpy(v.data() + o.v, B.v.data(), sizeof(B.v[0]) * B.v.size()); } while (0)
-        PUT(pose); PUT(free_of); PUT(adj_ptr); PUT(adj); PUT(start); PUT(rowptr); PUT(colptr); PUT(colrows); PUT(edges);
-#undef PUT
-        B = GraphBuild();
-    };
-    // write back (pose_graph.cpp:362-407): updatePose, updateCov, the update() calls, drift, the keyframes after cur
-    auto write_back = [&](int g) {
-        const int n = ns[g]; isv_pg_keyframe_t *kf = kfs[g];
-        const PgGraph &G = graphs[g];
-        isv_pgo_result_t &R = results[g];
-        R.n_loop_edges = n_loops[g];
-        const int param_index = G.P1 - 1;
-        isv_pg_keyframe_t *last = nullptr; const double *last_pose = nullptr;
-        for (int k = 0; k < n; k++) {
-            const int li = local[g][k]; if (li < 0) continue;
-            const double *p = pose.data() + (size_t)(G.pose0 + li) * 7;
-            memcpy(kf[k].T_w_i, p, 24); h_q2R(HQ{p[6], p[3], p[4], p[5]}, kf[k].R_w_i);
-            // (a graph whose covariance factorisation failed -- status ISV_ERR_NONFINITE -- keeps its keyframes' cov /
-            // cov_computed as they were: the reference does not check ceres::Covariance::Compute's result and would
-            // store whatever GetCovarianceBlock left; zeros marked "computed" are worse than no covariance)
-            if (li < param_index && R.status == ISV_OK) {
-                // ceres::Covariance::GetCovarianceBlock returns the 7x7 AMBIENT block [Sigma 0; 0 0]; the reference receives it in a
-                // 36-double buffer and maps that as a column-major 6x6 (pose_graph.cpp:346-350): reproduced, stored row-major
-                double c7[49] = {0};
-                const double *S6 = cov.data() + (size_t)(G.pose0 + li) * 36;
-                for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) c7[a * 7 + b] = S6[a * 6 + b];
-                for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) kf[k].cov[a * 6 + b] = c7[a + 6 * b];
-                kf[k].cov_computed = 1;
-            }
-            if (last) h_relpose_update(&last->relative_pose, last->T_w_i, last->R_w_i, kf[k].T_w_i, kf[k].R_w_i, last_pose, p);
-            last = &kf[k]; last_pose = p;
-        }
-        const isv_pg_keyframe_t &c = kf[cur_pos[g]];
-        double yc[3], yv[3], vT[9], t[3];
-        h_R2ypr(c.R_w_i, yc); h_R2ypr(c.vio_R_w_i, yv);
-        R.yaw_drift = yc[0] - yv[0];
-        for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) vT[a * 3 + b] = c.vio_R_w_i[b * 3 + a];
-        h_mm(c.R_w_i, vT, R.r_drift);
-        h_mv(R.r_drift, c.vio_T_w_i, t);
-        for (int k = 0; k < 3; k++) R.t_drift[k] = c.T_w_i[k] - t[k];
-        for (int k = cur_pos[g] + 1; k < n; k++) {
-            double Pn[3], Rn[9];
-            h_mv(R.r_drift, kf[k].vio_T_w_i, Pn); for (int dd = 0; dd < 3; dd++) Pn[dd] += R.t_drift[dd];
-            h_mm(R.r_drift, kf[k].vio_R_w_i, Rn);
-            memcpy(kf[k].T_w_i, Pn, 24); memcpy(kf[k].R_w_i, Rn, 72);
-        }
-    };
-    std::chrono::steady_clock::time_point tp2 = tp1, tp3 = tp1;      // (trace: the last chunk's enqueue, the last chunk's drain)
-    std::chrono::steady_clock::time_point t_enq[isv_pgo::PG_CHUNKS], t_done[isv_pgo::PG_CHUNKS];
-    {
-        int T = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-        if (const char *ev = getenv("ISV_HOST_THREADS")) T = atoi(ev);
-        T = std::max(1, std::min(T, ng));
-        std::atomic<int> next{0};
-        auto worker = [&] {
-            for (int id; (id = next.fetch_add(1)) < 2 * ng; ) {
-                if (id < ng) {
-                    const int g = id, c = chunk_of(g);
-                    if (fail_rc.load() == ISV_OK) assemble(g);
-                    if (left[c].fetch_sub(1) == 1) {
-                        if (fail_rc.load() == ISV_OK) enqueue_chunk(c);
-                        t_enq[c] = std::chrono::steady_clock::now();
-                        if (c == C - 1) tp2 = std::chrono::steady_clock::now();
-                        enq[c].store(1);
-                    }
-                } else {
-                    const int g = id - ng, c = chunk_of(g);
-                    if (!done[c].load()) {
-                        std::lock_guard<std::mutex> lk(done_mu[c]);
-                        if (!done[c].load()) {
-                            while (!enq[c].load()) std::this_thread::yield();
-                            if (fail_rc.load() == ISV_OK) {
-                                const hipError_t e1 = hipSetDevice(h->device), e2 = e1 == hipSuccess ? hipStreamSynchronize(h->cstream[c]) : e1;
-                                if (e2 != hipSuccess) fail(ISV_ERR_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e2));
-                                else memcpy(results + chunk_lo(c), res_stage + chunk_lo(c), sizeof(isv_pgo_result_t) * (size_t)(chunk_lo(c + 1) - chunk_lo(c)));
-                            }
-                            t_done[c] = std::chrono::steady_clock::now();
-                            if (c == C - 1) tp3 = std::chrono::steady_clock::now();
-                            done[c].store(1);
-                        }
-                    }
-                    if (fail_rc.load() == ISV_OK) write_back(g);
-                }
-            }
-        };
-        if (T == 1) worker();
-        else {
-            std::vector<std::thread> th;
-            for (int k = 0; k < T; k++) th.emplace_back(worker);
-            for (auto &x : th) x.join();
-        }
-    }
-#undef TCHK
-    if (fail_rc.load() != ISV_OK) {
-        for (int c = 0; c < C; c++) (void)hipStreamSynchronize(h->cstream[c]);      // nothing of this call stays in flight
-        return fail_rc.load();
-    }
-    {
-        // the span of the chunks' kernels: the chunk enqueued first starts first
-        float best = 0;
-        const int fc = first_chunk.load() < 0 ? 0 : first_chunk.load();
-        for (int c = 0; c < C; c++) { float f = 0; if (hipEventElapsedTime(&f, h->kev[fc][0], h->kev[c][1]) == hipSuccess) best = std::max(best, f); else (void)hipGetLastError(); }
-        h->last_kernel_ms = best;
-    }
-    if (getenv("ISV_TRACE_HANDOVER")) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "isv pgo batch: %d graphs: analysis %.2f ms, assembly %.2f ms, H2D + kernel + D2H %.2f ms (%.1f MB up), write-back %.2f ms\n", ng, ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3),
-                (pose.size() * 8 + edges.size() * sizeof(PgEdge) + (free_of.size() + adj_ptr.size() + adj.size() + start.size() + rowptr.size() + colptr.size() + colrows.size()) * 4) / 1e6, ms(tp3, std::chrono::steady_clock::now()));
-        const int fc = first_chunk.load() < 0 ? 0 : first_chunk.load();
-        for (int c = 0; c < C; c++) {       // every chunk's kernel on the first chunk's clock, and when the host enqueued / found it drained
-            float a = 0, b = 0;
-            (void)hipEventElapsedTime(&a, h->kev[fc][0], h->kev[c][0]); (void)hipEventElapsedTime(&b, h->kev[fc][0], h->kev[c][1]); (void)hipGetLastError();
-            fprintf(stderr, "  chunk %d: graphs [%d, %d): enqueued at %.2f ms, k_pgo %.2f .. %.2f ms after the first chunk's start, drained at %.2f ms\n", c, chunk_lo(c), chunk_lo(c + 1),
-                    ms(tp0, t_enq[c]), a, b, ms(tp0, t_done[c]));
-        }
-    }
-    // per-graph failures surface in the return value too (every graph has been written back by now; results[g].status says which)
-    for (int g = 0; g < ng; g++) if (results[g].status != ISV_OK) { h->err = "pose graph " + std::to_string(g) + ": the covariance factorisation failed (poses written, covariances left untouched)"; return results[g].status; }
-    return ISV_OK;
+    // 6. kernel time, trace
+    const int fc = first_chunk.load() < 0 ? 0 : first_chunk.load();
+    pgo_kernel_time(h, call.C, fc);
+    if (getenv("ISV_TRACE_HANDOVER")) pgo_trace(h, call, tm, fc, tp0, tp1);
+    // 7. per-graph status
+    return pg_batch_status(call, h->err);
 }
 
 extern "C" int isv_pgo_optimize(isv_pgo_t *h, int32_t n, isv_pg_keyframe_t *kf, int32_t first_looped_index, int32_t cur_index, isv_pgo_result_t *result) {
