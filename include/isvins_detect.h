@@ -8,7 +8,8 @@
  * successful tracking item is cur_img.  Detection moves no image: it uploads the surviving points and downloads the corners.
  * The first frame of a sequence (prev_img.empty()): seed the slot with a tracking item without points and prev == cur, then detect with n_points = 0.
  *
- * Not here: rejectWithF and CLAHE, the fisheye mask, and the host bookkeeping (ids, track_cnt++, velocities).
+ * Not here: rejectWithF, the fisheye mask, and the host bookkeeping (ids, track_cnt++, velocities).  CLAHE is isvins_equalize.h: a
+ * slot it wrote holds the equalised cur_img, which is what the reference detects on.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (imgproc: featureselect.cpp, corner.cpp, drawing.cpp, thresh.cpp).
  * OpenCV is not available to this project, so the restatement cannot be checked against it.  The CPU restatement

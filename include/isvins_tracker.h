@@ -6,8 +6,9 @@
  * one call (MI355X).  A sequence's tracker state, the image pyramid of its last `cur` image, stays on the device in a SLOT: the steady
  * state uploads one image and builds one pyramid per frame.
  *
- * Not here: setMask and goodFeaturesToTrack are isvins_detect.h, on this handle's slots; rejectWithF and CLAHE are nowhere yet; the
- * host bookkeeping, that is the compaction (reduceVector), track_cnt++, ids and the velocity map, stays with the caller.
+ * Not here: setMask and goodFeaturesToTrack are isvins_detect.h and CLAHE is isvins_equalize.h, both on this handle's slots;
+ * rejectWithF is nowhere yet; the host bookkeeping, that is the compaction (reduceVector), track_cnt++, ids and the velocity map,
+ * stays with the caller.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (video: lkpyramid.cpp; imgproc: pyramids.cpp; core: copy.cpp) and from
  * PinholeCamera.cc:461-521, :657-673.  OpenCV is not available to this project, so the restatement cannot be checked against it.  The
@@ -77,7 +78,8 @@ typedef enum isv_trk_status {
     ISV_TRK_CAPACITY = 1,         /* width > max_width, height > max_height, n_points > max_points */
     ISV_TRK_INPUT = 2             /* sizes below 1, a negative count, stride < width, a slot outside [0, max_slots), a null array with a
                                      non-zero size, a non-finite point; prev == NULL on an empty slot or on a slot whose resident image
-                                     has another size; a slot that another item of the same call names as well */
+                                     has another size or was written by an equaliser (isvins_equalize.h); a slot that another item of
+                                     the same call names as well */
 } isv_trk_status_t;
 
 #define ISV_TRK_FLAG_STATUS 1     /* bit 0 of flags: calcOpticalFlowPyrLK's status */

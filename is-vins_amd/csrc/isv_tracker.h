@@ -1,6 +1,7 @@
 // isv_tracker.h -- internal to the feature tracking (isv_tracker.hip), outside include/: the debug read-back of a slot's pyramids,
 // so that the tests report a wrong pyramid as a wrong pyramid rather than as wrong tracks; and the tracker handle itself with its
-// slots, which the feature detection (isv_detect.hip) reads: a detector works on level 0 of a slot's resident pyramid.
+// slots, which the feature detection (isv_detect.hip) reads: a detector works on level 0 of a slot's resident pyramid; and the one
+// body of the tracking call, which the CLAHE (isv_equalize.hip) runs with its kernels in place of the level-0 copy.
 #pragma once
 #include "../../include/isvins_tracker.h"
 
@@ -29,7 +30,13 @@ struct TrkShape {                 // a pyramid's levels: sizes and packed offset
     int32_t nlev, pad;
 };
 
-struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0; };      // par: which of the slot's two buffers is resident
+struct TrkJob {                   // one pyramid to build: an uploaded image -> a slot buffer
+    uint64_t src_off, dst_off;    // into the upload block's images; into the store
+    TrkShape s;
+};
+
+// par: which of the slot's two buffers is resident; tag: who wrote it, 0 a raw image (isv_trk_track_batch), else an equaliser's id
+struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0, tag = 0; };
 
 struct isv_trk : StageHandle {
     isv_trk_config_t cfg;
@@ -41,8 +48,15 @@ struct isv_trk : StageHandle {
     std::vector<int32_t> named;   // [max_slots]: how many good items of the call name the slot (valid where stamp is the call's serial)
     std::vector<int64_t> stamp;
     int64_t serial = 0;
+    int32_t eq_ids = 0;           // equalisers created on this handle so far: the next one's id is eq_ids + 1
     std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
     // the store offset of a slot's buffer; level 0 of a pyramid is at its start
     size_t store_off(int slot_i, int buf) const { return ((size_t)slot_i * 2 + buf) * slot_bytes; }
 };
+
+struct isv_eq;
+// isv_trk_track_batch's body (`entry` names the caller).  eq == nullptr: the raw images become level 0, on the handle's own stage
+// slot.  Otherwise the equaliser's kernels write level 0 (isv_equalize.h), and the call's block, times and error text are the equaliser's.
+int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results,
+                    float *const *cur_pts, uint8_t *const *flags, float *const *err, float *const *cur_un_pts);
 #endif

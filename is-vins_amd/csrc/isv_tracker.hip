@@ -8,6 +8,9 @@
 // the next cur image is built into; a successful item swaps them.  An uploaded prev is built over the resident one, which it
 // replaces anyway.  Every refusal is decided on the host before anything is launched: a refused item is not on the device at all.
 //
+// The call's body is trk_track_batch: isv_trk_track_batch runs it as it is, isv_eq_track_batch (isv_equalize.hip) with the CLAHE
+// kernels in place of k_trk_level0.  A slot remembers in its tag which of the two wrote its resident image.
+//
 // k_trk_level0: copies an uploaded image into level 0 of its pyramid buffer (16-byte words, then the tail).
 // k_trk_pyrdown: one workgroup per 32 x 16 tile of level l; the 67 x 35 source pixels of level l - 1 go into LDS with
 // BORDER_REFLECT_101 applied on the way in, the row pass fills a 16-bit LDS plane of 35 x 32, the column pass reads it.  One launch per
@@ -27,6 +30,7 @@
 #include <vector>
 #include "isv_stage_launch.h"
 #include "isv_tracker.h"
+#include "isv_equalize.h"
 #include "isv_pinhole.h"
 
 namespace {
@@ -39,11 +43,6 @@ constexpr int kPW = 32, kPH = 16, kPThreads = 256;    // k_trk_pyrdown's output 
 constexpr int kSrcW = 2 * kPW + 3, kSrcH = 2 * kPH + 3;
 constexpr int kCopyThreads = 256, kCopyBlocks = 32;   // k_trk_level0: blocks per image
 constexpr int kMaxSide = 8192, kMaxSlots = 65536, kMaxPoints = 65535;
-
-struct TrkJob {                   // one pyramid to build: an uploaded image -> a slot buffer
-    uint64_t src_off, dst_off;    // into the upload block's images; into the store
-    TrkShape s;
-};
 
 struct TrkItem {                  // one item that passed every check
     uint64_t prev_off, cur_off;   // the two pyramids, into the store
@@ -369,7 +368,13 @@ extern "C" int isv_trk_slot_reset(isv_trk_t *h, int32_t slot) {
 
 extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results, float *const *cur_pts,
                                    uint8_t *const *flags, float *const *err, float *const *cur_un_pts) {
-    StageCall call{h ? h->ctx() : StageCtx{}, "isv_trk_track_batch"};
+    return trk_track_batch(h, nullptr, "isv_trk_track_batch", n, items, results, cur_pts, flags, err, cur_un_pts);
+}
+
+int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results,
+                    float *const *cur_pts, uint8_t *const *flags, float *const *err, float *const *cur_un_pts) {
+    StageCall call{eq ? eq->ctx() : h ? h->ctx() : StageCtx{}, entry};
+    const int32_t tag = eq ? eq->id : 0;           // what the call writes into a slot, and what a resident prev has to be
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
     if (n > h->cfg.max_items) return call.fail(ISV_ERR_CAPACITY, "more items than max_items");
     if (!cur_pts || !flags || !err || !cur_un_pts) return call.fail(ISV_ERR_INVALID_ARG, "null output arrays");
@@ -383,7 +388,7 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
         if (s == ISV_TRK_OK && it->n_points > 0 && (!cur_pts[i] || !flags[i] || !err[i] || !cur_un_pts[i])) s = ISV_TRK_INPUT;
         if (s == ISV_TRK_OK && !it->prev) {
             const TrkSlot &sl = h->slots[it->slot];
-            if (!sl.valid || sl.W != it->width || sl.H != it->height) s = ISV_TRK_INPUT;
+            if (!sl.valid || sl.W != it->width || sl.H != it->height || sl.tag != tag) s = ISV_TRK_INPUT;
         }
         status[i] = s;
     }
@@ -397,7 +402,7 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
         if (status[i] == ISV_TRK_OK && h->named[items[i]->slot] > 1) status[i] = ISV_TRK_INPUT;
     std::vector<TrkItem> dev;
     std::vector<TrkJob> jobs;
-    std::vector<int> who;                          // dev[k] is items[who[k]]
+    std::vector<int> who, cur_job;                 // dev[k] is items[who[k]]; its cur image is jobs[cur_job[k]]
     size_t n_pt = 0, n_img = 0;
     int maxNp = 0, maxLev = 1, maxLW[kLevels] = {}, maxLH[kLevels] = {};
     for (int i = 0; i < n; i++) {
@@ -414,6 +419,7 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
         if (n_pt > INT32_MAX) return call.fail(ISV_ERR_CAPACITY, "batch too large");
         const size_t px = ((size_t)it->width * it->height + 15) & ~(size_t)15;
         if (it->prev) { jobs.push_back(TrkJob{n_img, T.prev_off, T.s}); n_img += px; }
+        cur_job.push_back((int)jobs.size());
         jobs.push_back(TrkJob{n_img, T.cur_off, T.s}); n_img += px;
         dev.push_back(T); who.push_back(i);
         if (T.np > maxNp) maxNp = T.np;
@@ -427,16 +433,18 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
     auto refuse = [&](int i) { results[i] = isv_trk_result_t{status[i], items[i]->n_points, 0, 0}; };
     if (m == 0) {
         for (int i = 0; i < n; i++) refuse(i);
+        if (eq) eq->last.assign(n, EqLast{});
         return ISV_OK;
     }
     // one upload block: [items | jobs | points | images, packed without their strides, each 16-byte aligned]; then, device only: a
-    // zeroed guard, cur_pts, cur_un_pts, err, flags of all points
+    // zeroed guard, cur_pts, cur_un_pts, err, flags of all points; with an equaliser, the LUTs of every job's tiles
     BlockLayout L;
     const size_t o_it = L.add(sizeof(TrkItem) * m), o_job = L.add(sizeof(TrkJob) * nj), o_pt = L.add(8 * (n_pt + 1)), o_img = L.add(n_img + 16);
     const size_t up_end = L.end;
     (void)L.add(16);
     const size_t clear_end = L.end;
     const size_t o_cp = L.add(8 * (n_pt + 1)), o_un = L.add(8 * (n_pt + 1)), o_er = L.add(4 * (n_pt + 1)), o_fl = L.add(n_pt + 1);
+    const size_t o_lut = eq ? L.add(eq->lut_bytes() * nj) : 0;
     const auto t_pack = std::chrono::steady_clock::now();
     std::vector<char> &up = h->up;
     up.resize(up_end);
@@ -456,7 +464,11 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
         up, {{up.size(), clear_end}}, L.end,
         [&](char *d, auto &&mark) {
             const TrkJob *dj = (const TrkJob *)(d + o_job);
-            hipLaunchKernelGGL(k_trk_level0, dim3(nj, kCopyBlocks), dim3(kCopyThreads), 0, stream, dj, (const uint8_t *)(d + o_img), h->d_store);
+            if (eq) {
+                eq_launch(*eq, stream, dj, nj, (const uint8_t *)(d + o_img), h->d_store, (uint8_t *)(d + o_lut), maxLW[0], maxLH[0]);
+                mark();
+            } else
+                hipLaunchKernelGGL(k_trk_level0, dim3(nj, kCopyBlocks), dim3(kCopyThreads), 0, stream, dj, (const uint8_t *)(d + o_img), h->d_store);
             for (int l = 1; l < maxLev; l++)
                 hipLaunchKernelGGL(k_trk_pyrdown, dim3(nj, (maxLW[l] + kPW - 1) / kPW, (maxLH[l] + kPH - 1) / kPH), dim3(kPThreads), 0, stream, dj, h->d_store, l);
             mark();
@@ -481,15 +493,24 @@ extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t
                     for (size_t p = 0; p < np; p++) kept += flags[i][p] == (ISV_TRK_FLAG_STATUS | ISV_TRK_FLAG_BORDER);
                 }
                 results[i] = isv_trk_result_t{ISV_TRK_OK, (int32_t)np, kept, dev[k].s.nlev};
-                h->slots[items[i]->slot] = TrkSlot{items[i]->width, items[i]->height, (int32_t)((dev[k].cur_off - h->store_off(items[i]->slot, 0)) / h->slot_bytes), 1};
+                h->slots[items[i]->slot] = TrkSlot{items[i]->width, items[i]->height, (int32_t)((dev[k].cur_off - h->store_off(items[i]->slot, 0)) / h->slot_bytes), 1, tag};
+            }
+            if (eq) {
+                eq->last.assign(n, EqLast{});
+                for (int k = 0; k < m; k++) {
+                    EqLast &l = eq->last[who[k]];
+                    l.lut_off[0] = (int64_t)(o_lut + eq->lut_bytes() * cur_job[k]);
+                    if (items[who[k]]->prev) l.lut_off[1] = (int64_t)(o_lut + eq->lut_bytes() * (cur_job[k] - 1));
+                }
             }
             return hipSuccess;
         });
     if (rc != ISV_OK) {                            // what the kernels left in the buffers is unknown
         for (int k = 0; k < m; k++) h->slots[items[who[k]]->slot] = TrkSlot{};
+        if (eq) eq->last.clear();
         return rc;
     }
-    h->pack_ms = pack_ms;
+    (eq ? eq->pack_ms : h->pack_ms) = pack_ms;
     return ISV_OK;
 }
 
