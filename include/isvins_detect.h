@@ -8,7 +8,8 @@
  * successful tracking item is cur_img.  Detection moves no image: it uploads the surviving points and downloads the corners.
  * The first frame of a sequence (prev_img.empty()): seed the slot with a tracking item without points and prev == cur, then detect with n_points = 0.
  *
- * Not here: rejectWithF, the fisheye mask, and the host bookkeeping (ids, track_cnt++, velocities).  CLAHE is isvins_equalize.h: a
+ * Not here: the fisheye mask and the host bookkeeping (ids, track_cnt++, velocities).  rejectWithF is isvins_reject.h, between the
+ * tracking call and this one.  CLAHE is isvins_equalize.h: a
  * slot it wrote holds the equalised cur_img, which is what the reference detects on.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (imgproc: featureselect.cpp, corner.cpp, drawing.cpp, thresh.cpp).
@@ -83,7 +84,7 @@ typedef struct isv_det_config {
 
 typedef struct isv_det_item {
     int32_t slot;                 /* a slot of the tracker handle; its resident image (level 0) is cur_img        */
-    int32_t n_points;             /* cur_pts after the caller's reduceVector (and rejectWithF, if it runs one)    */
+    int32_t n_points;             /* cur_pts after the caller's reduceVector (and after rejectWithF: isvins_reject.h) */
     int32_t max_new;              /* MAX_CNT - n_points as the reference computes it; 0: setMask only; < 0 refused */
     int32_t _pad;
     const float   *cur_pts;       /* [n_points][2]                                                                */

@@ -9,7 +9,7 @@
  * (isvins_detect.h), which reads level 0 of the resident pyramid, sees the equalised cur_img as in the reference (:104, :140).
  * isv_eq_apply_batch runs the same kernels on images that touch no slot and returns the equalised images.
  *
- * Not here: rejectWithF; the host bookkeeping stays with the caller.
+ * Not here: rejectWithF is isvins_reject.h; the host bookkeeping stays with the caller.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (imgproc: clahe.cpp, the 8-bit path; core: copy.cpp).  OpenCV is not
  * available to this project, so the restatement cannot be checked against it.  The CPU restatement tests/native/isv_eq_oracle.c pins

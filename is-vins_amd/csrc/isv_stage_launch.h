@@ -1,8 +1,8 @@
 // isv_stage_launch.h -- the host side every batched stage shares: the three initialisation stages on a backend handle
 // (isv_initial.hip, isv_sfm.hip, isv_relpose.hip), the loop-closure verification (isv_loop.hip), the loop detection
 // (isv_bow.hip), the keyframe extraction (isv_keyframe.hip) and the feature tracking (isv_tracker.hip), each of the four on its
-// own handle (StageHandle), and the feature detection (isv_detect.hip) and the CLAHE (isv_equalize.hip) on a tracker handle's device
-// and stream.
+// own handle (StageHandle), and the feature detection (isv_detect.hip), the CLAHE (isv_equalize.hip) and the outlier rejection
+// (isv_reject.hip) on a tracker handle's device and stream.
 // A stage call packs its problems into one pageable upload block, launches its kernels on the context's stream and copies its
 // outputs back, synchronously; the launcher owns the events around and between the kernels and the times read from them.  A stage
 // file keeps what is its own: its header record and problem checks, the packing, the kernel launch(es) with their marks and the
