@@ -7,8 +7,9 @@
  * state uploads one image and builds one pyramid per frame.
  *
  * Not here: setMask and goodFeaturesToTrack are isvins_detect.h and CLAHE is isvins_equalize.h, both on this handle's slots;
- * rejectWithF is isvins_reject.h, on this handle's device, stream and camera; the host bookkeeping, that is the compaction
- * (reduceVector), track_cnt++, ids and the velocity map, stays with the caller.
+ * rejectWithF is isvins_reject.h, on this handle's device, stream and camera; the bookkeeping, that is the compaction
+ * (reduceVector), track_cnt++, ids and the velocity map, stays with the caller of these stage calls -- or is isvins_frontend.h,
+ * which runs all of readImage in one call with the state on the device.
  *
  * The arithmetic is RESTATED from OpenCV 3.2.0 as published (video: lkpyramid.cpp; imgproc: pyramids.cpp; core: copy.cpp) and from
  * PinholeCamera.cc:461-521, :657-673.  OpenCV is not available to this project, so the restatement cannot be checked against it.  The

@@ -41,35 +41,9 @@ static_assert(kThreads * 2 == kTW * kTH, "k_det_eig: two pixels per thread");
 constexpr int kRawW = kTW + 4, kRawH = kTH + 4, kDW = kTW + 2, kDH = kTH + 2;
 constexpr int kSelThreads = 1024, kSelWaves = kSelThreads / kLanes, kSelRegs = 16;
 constexpr int kCandBlocks = 4096;                             // k_det_cand: at most this many workgroups per item, each strides
-constexpr int kMaxR = 255;
-
-struct DetItem {                  // one item that passed every check
-    uint64_t img_off;             // level 0 of the slot's resident pyramid, into the tracker's store
-    uint64_t mask_off, eig_off, key_off;      // the item's planes, into the call's block
-    int32_t W, H, np, pt_off;     // its ordered points: at pt_off of the points section (and of the kept section)
-    int32_t max_new, out_off;     // its corners: at out_off of the corner sections
-    int32_t pad[2];
-};
-struct DetPoint { int32_t x, y, idx, pad; };                  // the rounded pixel and the input index
-struct DetCount { uint32_t max_key, n_cand; int32_t n_kept, n_new; };     // zeroed before the kernels
-
-struct DetLast { int32_t W = 0, H = 0, valid = 0, has_eig = 0, n_cand = 0; size_t mask_off = 0, eig_off = 0; };
+constexpr int kMaxR = kDetMaxR;
 
 }  // namespace
-
-struct isv_det {
-    isv_det_config_t cfg;
-    isv_trk *trk = nullptr;
-    std::string err;
-    StageSlot slot;               // the call's device block (grow-only), events and times
-    StageCtx ctx() { return StageCtx{trk->device, trk->stream, &slot, &err}; }   // (the device and the stream are the tracker's)
-    uint8_t hw[kMaxR + 1];        // the disc of radius min_dist: the half-width per |dy|
-    std::vector<char> up;
-    std::vector<DetLast> last;    // the last call's items, for the debug read-back
-    std::vector<int32_t> named;   // as the tracker's
-    std::vector<int64_t> stamp;
-    int64_t serial = 0;
-};
 
 // BORDER_REFLECT_101, the general loop: always inside [0, len)
 __device__ __forceinline__ int det_reflect(int p, int len) {
@@ -301,13 +275,6 @@ void disc_table(int r, uint8_t hw[kMaxR + 1]) {
     }
 }
 
-// cvRound of a float32, half to even (the default rounding mode); outside int's range it does not exist
-bool round_coord(float f, int *out) {
-    if (!(f >= -2147483648.0f && f < 2147483648.0f)) return false;
-    *out = (int)lrintf(f);
-    return true;
-}
-
 }  // namespace
 
 extern "C" const char *isv_det_last_error(const isv_det_t *h) { return h ? h->err.c_str() : "null handle"; }
@@ -347,6 +314,21 @@ extern "C" int isv_det_last_ms(isv_det_t *h, double out_ms[5]) {
     return ISV_OK;
 }
 
+void det_enqueue(isv_det *h, const DetItem *di, int m, const DetPoint *d_pts, const uint8_t *d_hw, char *d, DetCount *dc, int32_t *d_kept, float *d_new, float *d_un,
+                 int any_new, int maxW, int maxH, size_t maxPix, const std::function<void()> &mark) {
+    isv_trk *trk = h->trk;
+    hipStream_t stream = trk->stream;
+    hipLaunchKernelGGL(k_det_mask, dim3(m), dim3(kThreads), 0, stream, di, d_pts, d_hw, d, dc, d_kept, h->cfg.min_dist);
+    mark();
+    if (any_new) {
+        const size_t cb = (maxPix + kThreads - 1) / kThreads;
+        hipLaunchKernelGGL(k_det_eig, dim3(m, (maxW + kTW - 1) / kTW, (maxH + kTH - 1) / kTH), dim3(kThreads), 0, stream, di, (const uint8_t *)trk->d_store, d, dc);
+        mark();
+        hipLaunchKernelGGL(k_det_cand, dim3(m, (unsigned)(cb < (size_t)kCandBlocks ? cb : (size_t)kCandBlocks)), dim3(kThreads), 0, stream, di, d, dc, h->cfg.quality_level);
+        hipLaunchKernelGGL(k_det_select, dim3(m), dim3(kSelThreads), 0, stream, di, d, dc, trk->cam, d_new, d_un, h->cfg.min_dist);
+    } else mark();
+}
+
 extern "C" int isv_det_detect_batch(isv_det_t *h, int32_t n, const isv_det_item_t *const *items, isv_det_result_t *results, int32_t *const *kept_index,
                                     float *const *new_pts, float *const *new_un_pts) {
     StageCall call{h ? h->ctx() : StageCtx{}, "isv_det_detect_batch"};
@@ -373,7 +355,7 @@ extern "C" int isv_det_detect_batch(isv_det_t *h, int32_t n, const isv_det_item_
             for (int p = 0; p < it->n_points && s == ISV_DET_OK; p++) {
                 const float x = it->cur_pts[2 * p], y = it->cur_pts[2 * p + 1];
                 int rx, ry;
-                if (!std::isfinite(x) || !std::isfinite(y) || !round_coord(x, &rx) || !round_coord(y, &ry) || rx < 0 || rx >= sl.W || ry < 0 || ry >= sl.H)
+                if (!std::isfinite(x) || !std::isfinite(y) || !det_round_coord(x, &rx) || !det_round_coord(y, &ry) || rx < 0 || rx >= sl.W || ry < 0 || ry >= sl.H)
                     s = ISV_DET_INPUT;
                 else pix[i][p] = DetPoint{rx, ry, p, 0};
             }
@@ -446,25 +428,14 @@ extern "C" int isv_det_detect_batch(isv_det_t *h, int32_t n, const isv_det_item_
         std::stable_sort(p.begin(), p.end(), [cnt](const DetPoint &a, const DetPoint &b) { return cnt[a.idx] > cnt[b.idx]; });     // G1
         if (!p.empty()) memcpy(up.data() + o_pt + sizeof(DetPoint) * (size_t)dev[k].pt_off, p.data(), sizeof(DetPoint) * p.size());
     }
-    hipStream_t stream = trk->stream;
     std::vector<DetCount> cnt(m);
     std::vector<int32_t> dl_kept(n_pt + 1);
     std::vector<float> dl_np(2 * (n_out + 1)), dl_un(2 * (n_out + 1));
     const int rc = call.run(
         up, {{up_end, clear_end}, {o_mask, o_mask + mask_bytes, 0xff}}, L.end,
         [&](char *d, auto &&mark) {
-            const DetItem *di = (const DetItem *)(d + o_it);
-            DetCount *dc = (DetCount *)(d + o_cnt);
-            hipLaunchKernelGGL(k_det_mask, dim3(m), dim3(kThreads), 0, stream, di, (const DetPoint *)(d + o_pt), (const uint8_t *)(d + o_hw), d, dc,
-                               (int32_t *)(d + o_kept), cfg.min_dist);
-            mark();
-            if (any_new) {
-                const size_t cb = (maxPix + kThreads - 1) / kThreads;
-                hipLaunchKernelGGL(k_det_eig, dim3(m, (maxW + kTW - 1) / kTW, (maxH + kTH - 1) / kTH), dim3(kThreads), 0, stream, di, (const uint8_t *)trk->d_store, d, dc);
-                mark();
-                hipLaunchKernelGGL(k_det_cand, dim3(m, (unsigned)(cb < (size_t)kCandBlocks ? cb : (size_t)kCandBlocks)), dim3(kThreads), 0, stream, di, d, dc, cfg.quality_level);
-                hipLaunchKernelGGL(k_det_select, dim3(m), dim3(kSelThreads), 0, stream, di, d, dc, trk->cam, (float *)(d + o_np), (float *)(d + o_un), cfg.min_dist);
-            } else mark();
+            det_enqueue(h, (const DetItem *)(d + o_it), m, (const DetPoint *)(d + o_pt), (const uint8_t *)(d + o_hw), d, (DetCount *)(d + o_cnt), (int32_t *)(d + o_kept),
+                        (float *)(d + o_np), (float *)(d + o_un), any_new, maxW, maxH, maxPix, mark);
         },
         {{cnt.data(), o_cnt, sizeof(DetCount) * m}, {n_pt ? dl_kept.data() : nullptr, o_kept, 4 * n_pt}, {n_out ? dl_np.data() : nullptr, o_np, 8 * n_out},
          {n_out ? dl_un.data() : nullptr, o_un, 8 * n_out}},

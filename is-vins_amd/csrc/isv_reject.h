@@ -87,5 +87,15 @@ struct isv_rej {
     StageCtx ctx() { return StageCtx{trk->device, trk->stream, &slot, &err}; }   // (the device and the stream are the tracker's)
     std::vector<char> up;
 };
+
+struct RejHdr {                   // per-item record
+    int64_t pt_off;               // the item's first point: into the points (4 floats each) and into the status bytes
+    int32_t n, pad;
+    double half_w, half_h;        // COL / 2.0, ROW / 2.0
+};
+
+// k_rej_f on `m` device-resident records, on the tracker's stream (isv_rej_reject_batch's launch, and isv_frontend.hip's): the points of
+// record k are d_pts + 4 * pt_off, prev [n][2] then cur [n][2]; max_n bounds every record's n (the kernel's dynamic LDS)
+void rej_enqueue(isv_rej *h, const RejHdr *d_hdrs, int m, int max_n, const float *d_pts, isv_rej_result_t *d_results, uint8_t *d_status);
 #endif
 #endif /* ISV_REJECT_H */

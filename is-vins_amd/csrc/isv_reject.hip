@@ -27,12 +27,6 @@ namespace {
 
 constexpr int kLanes = 64;
 
-struct RejHdr {                   // host-packed per-item record
-    int64_t pt_off;               // the item's first point: into the points (4 floats each) and into the status bytes
-    int32_t n, pad;
-    double half_w, half_h;        // COL / 2.0, ROW / 2.0
-};
-
 struct RejParams {
     PinholeCam cam;
     double focal, thresh;
@@ -210,6 +204,13 @@ extern "C" int isv_rej_last_ms(isv_rej_t *h, double out_ms[4]) {
     return ISV_OK;
 }
 
+void rej_enqueue(isv_rej *h, const RejHdr *d_hdrs, int m, int max_n, const float *d_pts, isv_rej_result_t *d_results, uint8_t *d_status) {
+    RejParams P;
+    memset(&P, 0, sizeof(P));
+    P.cam = h->trk->cam; P.focal = h->cfg.focal_length; P.thresh = h->cfg.f_threshold;
+    hipLaunchKernelGGL(k_rej_f, dim3(m), dim3(kLanes), sizeof(float4) * (size_t)max_n, h->trk->stream, d_hdrs, d_pts, d_results, d_status, P);
+}
+
 extern "C" int isv_rej_reject_batch(isv_rej_t *h, int32_t n, const isv_rej_item_t *const *items, isv_rej_result_t *results, uint8_t *const *status) {
     StageCall call{h ? h->ctx() : StageCtx{}, "isv_rej_reject_batch"};
     if (const int rc = call.enter(n, items, results); rc != ISV_OK || n == 0) return rc;
@@ -254,17 +255,12 @@ extern "C" int isv_rej_reject_batch(isv_rej_t *h, int32_t n, const isv_rej_item_
         memcpy(dst + 8 * (size_t)it->n_points, it->cur_pts, 8 * (size_t)it->n_points);
     }
     const double pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pack).count();
-    RejParams P;
-    memset(&P, 0, sizeof(P));
-    P.cam = h->trk->cam; P.focal = h->cfg.focal_length; P.thresh = h->cfg.f_threshold;
-    hipStream_t stream = h->trk->stream;
     std::vector<isv_rej_result_t> rm(m);
     std::vector<uint8_t> sm(n_pt + 1);
     const int rc = call.run(
         up, {}, L.end,
         [&](char *d, auto &&) {
-            hipLaunchKernelGGL(k_rej_f, dim3(m), dim3(kLanes), sizeof(float4) * (size_t)max_n, stream, (const RejHdr *)(d + o_hd), (const float *)(d + o_pt),
-                               (isv_rej_result_t *)(d + o_res), (uint8_t *)(d + o_st), P);
+            rej_enqueue(h, (const RejHdr *)(d + o_hd), m, max_n, (const float *)(d + o_pt), (isv_rej_result_t *)(d + o_res), (uint8_t *)(d + o_st));
         },
         {{rm.data(), o_res, sizeof(isv_rej_result_t) * m}, {n_pt ? sm.data() : nullptr, o_st, n_pt}},
         [&] {

@@ -19,6 +19,7 @@ int isv_internal_trk_read_level(isv_trk_t *h, int32_t slot, int32_t which, int32
 #endif
 
 #ifdef __HIPCC__
+#include <functional>
 #include "isv_stage_launch.h"
 #include "isv_pinhole.h"
 
@@ -35,6 +36,12 @@ struct TrkJob {                   // one pyramid to build: an uploaded image -> 
     TrkShape s;
 };
 
+struct TrkItem {                  // one item that passed every check
+    uint64_t prev_off, cur_off;   // the two pyramids, into the store
+    TrkShape s;
+    int32_t np, pt_off, pad[2];
+};
+
 // par: which of the slot's two buffers is resident; tag: who wrote it, 0 a raw image (isv_trk_track_batch), else an equaliser's id
 struct TrkSlot { int32_t W = 0, H = 0, par = 0, valid = 0, tag = 0; };
 
@@ -47,6 +54,7 @@ struct isv_trk : StageHandle {
     std::vector<TrkSlot> slots;
     std::vector<int32_t> named;   // [max_slots]: how many good items of the call name the slot (valid where stamp is the call's serial)
     std::vector<int64_t> stamp;
+    std::vector<int64_t> gen;     // [max_slots]: bumped whenever a slot's resident image is replaced or dropped (isv_frontend.hip compares it)
     int64_t serial = 0;
     int32_t eq_ids = 0;           // equalisers created on this handle so far: the next one's id is eq_ids + 1
     std::vector<char> up;         // the upload block's host image (grow-only: an image batch is large)
@@ -59,4 +67,12 @@ struct isv_eq;
 // slot.  Otherwise the equaliser's kernels write level 0 (isv_equalize.h), and the call's block, times and error text are the equaliser's.
 int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results,
                     float *const *cur_pts, uint8_t *const *flags, float *const *err, float *const *cur_un_pts);
+
+// The launch sequence of that body, on device-resident records, for isv_frontend.hip as well: the level-0 kernels (the CLAHE's with eq,
+// which then calls mark() behind them) and k_trk_pyrdown per level on `nj` jobs; then k_trk_track on `m` items, a grid of max_np points
+// per item (a lane beyond an item's np returns at once).  Everything goes on the handle's stream.
+TrkShape trk_make_shape(int W, int H);
+void trk_enqueue_pyramids(isv_trk *h, isv_eq *eq, const TrkJob *d_jobs, int nj, const uint8_t *d_img, uint8_t *d_lut, int maxLev, const int *maxLW, const int *maxLH,
+                          const std::function<void()> &mark);
+void trk_enqueue_track(isv_trk *h, const TrkItem *d_items, int m, int max_np, const float *d_pts, float *d_cur, float *d_un, float *d_err, uint8_t *d_flags);
 #endif

@@ -44,13 +44,9 @@ constexpr int kSrcW = 2 * kPW + 3, kSrcH = 2 * kPH + 3;
 constexpr int kCopyThreads = 256, kCopyBlocks = 32;   // k_trk_level0: blocks per image
 constexpr int kMaxSide = 8192, kMaxSlots = 65536, kMaxPoints = 65535;
 
-struct TrkItem {                  // one item that passed every check
-    uint64_t prev_off, cur_off;   // the two pyramids, into the store
-    TrkShape s;
-    int32_t np, pt_off, pad[2];
-};
+}  // namespace
 
-TrkShape make_shape(int W, int H) {
+TrkShape trk_make_shape(int W, int H) {
     TrkShape s;
     memset(&s, 0, sizeof(s));
     s.lw[0] = W; s.lh[0] = H; s.nlev = 1;
@@ -62,6 +58,10 @@ TrkShape make_shape(int W, int H) {
     }
     return s;
 }
+
+namespace {
+
+TrkShape make_shape(int W, int H) { return trk_make_shape(W, H); }
 size_t shape_bytes(const TrkShape &s) { return (size_t)s.lo[s.nlev - 1] + (size_t)s.lw[s.nlev - 1] * s.lh[s.nlev - 1]; }
 
 }  // namespace
@@ -343,6 +343,7 @@ extern "C" int isv_trk_create(const isv_trk_config_t *c, isv_trk_t **out) {
     h->slots.resize(c->max_slots);
     h->named.assign(c->max_slots, 0);
     h->stamp.assign(c->max_slots, 0);
+    h->gen.assign(c->max_slots, 0);
     hipError_t e = h->open();
     if (e == hipSuccess) e = hipMalloc(&h->d_store, h->slot_bytes * 2 * (size_t)c->max_slots);
     if (stage_open_failed("isv_trk_create", e)) {
@@ -363,12 +364,30 @@ extern "C" int isv_trk_last_ms(isv_trk_t *h, double out_ms[5]) {
 extern "C" int isv_trk_slot_reset(isv_trk_t *h, int32_t slot) {
     if (!h || slot < 0 || slot >= h->cfg.max_slots) return ISV_ERR_INVALID_ARG;
     h->slots[slot] = TrkSlot{};
+    h->gen[slot]++;
     return ISV_OK;
 }
 
 extern "C" int isv_trk_track_batch(isv_trk_t *h, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results, float *const *cur_pts,
                                    uint8_t *const *flags, float *const *err, float *const *cur_un_pts) {
     return trk_track_batch(h, nullptr, "isv_trk_track_batch", n, items, results, cur_pts, flags, err, cur_un_pts);
+}
+
+void trk_enqueue_pyramids(isv_trk *h, isv_eq *eq, const TrkJob *dj, int nj, const uint8_t *d_img, uint8_t *d_lut, int maxLev, const int *maxLW, const int *maxLH,
+                          const std::function<void()> &mark) {
+    hipStream_t stream = h->stream;
+    if (eq) {
+        eq_launch(*eq, stream, dj, nj, d_img, h->d_store, d_lut, maxLW[0], maxLH[0]);
+        mark();
+    } else
+        hipLaunchKernelGGL(k_trk_level0, dim3(nj, kCopyBlocks), dim3(kCopyThreads), 0, stream, dj, d_img, h->d_store);
+    for (int l = 1; l < maxLev; l++)
+        hipLaunchKernelGGL(k_trk_pyrdown, dim3(nj, (maxLW[l] + kPW - 1) / kPW, (maxLH[l] + kPH - 1) / kPH), dim3(kPThreads), 0, stream, dj, h->d_store, l);
+}
+
+void trk_enqueue_track(isv_trk *h, const TrkItem *d_items, int m, int max_np, const float *d_pts, float *d_cur, float *d_un, float *d_err, uint8_t *d_flags) {
+    if (max_np > 0)
+        hipLaunchKernelGGL(k_trk_track, dim3(max_np, m), dim3(kLanes), 0, h->stream, d_items, d_pts, (const uint8_t *)h->d_store, h->cam, d_cur, d_un, d_err, d_flags);
 }
 
 int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const isv_trk_item_t *const *items, isv_trk_result_t *results,
@@ -457,24 +476,15 @@ int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const 
         pack_image(up.data() + o_img + jobs[j++].src_off, it->cur, it->width, it->height, it->stride);
     }
     const double pack_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pack).count();
-    hipStream_t stream = h->stream;
     std::vector<char> dl(21 * n_pt + 32);
     const size_t b_cp = 0, b_un = 8 * n_pt, b_er = 16 * n_pt, b_fl = 20 * n_pt;
     const int rc = call.run(
         up, {{up.size(), clear_end}}, L.end,
         [&](char *d, auto &&mark) {
-            const TrkJob *dj = (const TrkJob *)(d + o_job);
-            if (eq) {
-                eq_launch(*eq, stream, dj, nj, (const uint8_t *)(d + o_img), h->d_store, (uint8_t *)(d + o_lut), maxLW[0], maxLH[0]);
-                mark();
-            } else
-                hipLaunchKernelGGL(k_trk_level0, dim3(nj, kCopyBlocks), dim3(kCopyThreads), 0, stream, dj, (const uint8_t *)(d + o_img), h->d_store);
-            for (int l = 1; l < maxLev; l++)
-                hipLaunchKernelGGL(k_trk_pyrdown, dim3(nj, (maxLW[l] + kPW - 1) / kPW, (maxLH[l] + kPH - 1) / kPH), dim3(kPThreads), 0, stream, dj, h->d_store, l);
+            trk_enqueue_pyramids(h, eq, (const TrkJob *)(d + o_job), nj, (const uint8_t *)(d + o_img), eq ? (uint8_t *)(d + o_lut) : nullptr, maxLev, maxLW, maxLH, mark);
             mark();
-            if (maxNp > 0)
-                hipLaunchKernelGGL(k_trk_track, dim3(maxNp, m), dim3(kLanes), 0, stream, (const TrkItem *)(d + o_it), (const float *)(d + o_pt),
-                                   (const uint8_t *)h->d_store, h->cam, (float *)(d + o_cp), (float *)(d + o_un), (float *)(d + o_er), (uint8_t *)(d + o_fl));
+            trk_enqueue_track(h, (const TrkItem *)(d + o_it), m, maxNp, (const float *)(d + o_pt), (float *)(d + o_cp), (float *)(d + o_un), (float *)(d + o_er),
+                              (uint8_t *)(d + o_fl));
         },
         {{n_pt ? dl.data() + b_cp : nullptr, o_cp, 8 * n_pt}, {n_pt ? dl.data() + b_un : nullptr, o_un, 8 * n_pt}, {n_pt ? dl.data() + b_er : nullptr, o_er, 4 * n_pt},
          {n_pt ? dl.data() + b_fl : nullptr, o_fl, n_pt}},
@@ -494,6 +504,7 @@ int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const 
                 }
                 results[i] = isv_trk_result_t{ISV_TRK_OK, (int32_t)np, kept, dev[k].s.nlev};
                 h->slots[items[i]->slot] = TrkSlot{items[i]->width, items[i]->height, (int32_t)((dev[k].cur_off - h->store_off(items[i]->slot, 0)) / h->slot_bytes), 1, tag};
+                h->gen[items[i]->slot]++;
             }
             if (eq) {
                 eq->last.assign(n, EqLast{});
@@ -506,7 +517,7 @@ int trk_track_batch(isv_trk *h, isv_eq *eq, const char *entry, int32_t n, const 
             return hipSuccess;
         });
     if (rc != ISV_OK) {                            // what the kernels left in the buffers is unknown
-        for (int k = 0; k < m; k++) h->slots[items[who[k]]->slot] = TrkSlot{};
+        for (int k = 0; k < m; k++) { h->slots[items[who[k]]->slot] = TrkSlot{}; h->gen[items[who[k]]->slot]++; }
         if (eq) eq->last.clear();
         return rc;
     }
