@@ -45,10 +45,13 @@ __global__ void k_vector2double(DevBatch d) {
 }
 
 // ------------------------------------------------------------------------------------------
-// sqrt_info of every IMU factor.  The covariance is badly conditioned, so any change of
-// operation order moves the result by cond*eps; to stay comparable with the CPU restatement this
-// kernel keeps the textbook order (LU with partial pivoting, column-wise solves, Cholesky) and
-// forbids FMA contraction.  One wavefront per factor; the work is 15^3 and runs once per solve.
+// sqrt_info of every IMU factor.  The covariance's condition number, measured at EuRoC noise (numpy, 2-norm): 2.6e6 for
+// 2 to 20 samples at 5 ms (and at 2.5 ms, and at ten times the gyro rate), 3.3e6 for 200, 1.3e8 for the 2000 samples of
+// the sum_dt > 10 gate's edge; a one-sample pre-integration is singular.  A change of operation order moves
+// the result by cond * eps, so to stay comparable bit for bit with the CPU restatement this kernel keeps the textbook
+// order (LU with partial pivoting, column-wise solves, Cholesky) and forbids FMA contraction.  Against the 40-digit
+// cov^-1 and its Cholesky factor that order is as good as LAPACK's (tests/test_gpu_prep_highprec.py: U^T U to 3e-16 of
+// the largest entry, U's rows to 4e-16 .. 4e-14).  One wavefront per factor; the work is 15^3 and runs once per solve.
 #pragma clang fp contract(off)
 __global__ __launch_bounds__(64) void k_imu_prep(DevBatch d, const int32_t *sel) {
     __shared__ double A[225], Inv[225], L[225];
@@ -297,10 +300,14 @@ template __global__ void k_proj_linearize<1>(DevBatch, const double *, const dou
 
 // ------------------------------------------------------------------------------------------
 // FeatureManager::triangulate (src/feature_tracker/feature_manager.cpp:206-258), one lane per landmark that has no
-// positive depth yet: the DLT rows of all its views, expressed in the host camera frame, are accumulated as the 4x4
-// Gram matrix A^T A (the right singular vectors of A are its eigenvectors); a cyclic Jacobi eigen-solve in
-// registers gives the vector of the smallest singular value, depth = v[2] / v[3], clamped to INIT_DEPTH outside
-// [0.1, 8] like the reference.
+// positive depth yet.  The reference takes the JacobiSVD of the 2k x 4 DLT matrix A; here the two rows of every view,
+// expressed in the host camera frame, are streamed by Givens rotations into the 4 x 4 upper-triangular R of A = Q R (A and
+// R share their singular values and right singular vectors), and a one-sided (Hestenes) Jacobi on R's columns, R V = U S
+// with V accumulated from the rotations, gives the vector of the smallest singular value: depth = v[2] / v[3], INIT_DEPTH
+// outside [0.1, 8] like the reference.  Both steps are orthogonal transformations of A itself, so the depth carries
+// u sigma_1 / sigma_3 like any SVD; the eigenvectors of the Gram matrix A^T A, which this kernel used before, carry
+// u (sigma_1 / sigma_3)^2 (tests/test_gpu_prep_highprec.py: three digits lost at a 5 mm baseline).
+// Static indices only: R (10 doubles), the rotated copy (16) and V (16) stay in registers, no scratch.
 __global__ __launch_bounds__(64) void k_triangulate(DevBatch d) {
     const int l = blockIdx.x * 64 + threadIdx.x;
     if (l >= d.Ltot) return;
@@ -313,7 +320,11 @@ __global__ __launch_bounds__(64) void k_triangulate(DevBatch d) {
     m3_mul(Rs + 9 * h, ric, R0);
     m3v(Rs + 9 * h, tic, tt);
     for (int c = 0; c < 3; c++) t0[c] = Ps[3 * h + c] + tt[c];
-    double M[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // upper triangle of A^T A: (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+    double G[4][4];                                      // R of the rows seen so far (upper triangle), later R V
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) G[a][c] = 0.0;
     for (int o = 0; o < k; o++) {
         const int j = h + o;
         double R1[9], t1[3], dt[3], tr[3], R[9], P[12];
@@ -331,57 +342,58 @@ __global__ __launch_bounds__(64) void k_triangulate(DevBatch d) {
         else { const int f = f0 + o - 1; fx = d.f_pts_j[(size_t)f * 2]; fy = d.f_pts_j[(size_t)f * 2 + 1]; fz = d.f_pts_z[f]; }
         const double nrm = sqrt(fx * fx + fy * fy + fz * fz);
         fx /= nrm; fy /= nrm; fz /= nrm;
-        double ra[4], rb[4];
-        for (int c = 0; c < 4; c++) { ra[c] = fx * P[8 + c] - fz * P[c]; rb[c] = fy * P[8 + c] - fz * P[4 + c]; }
-        int e = 0;
+        double x[2][4];
 #pragma unroll
-        for (int a = 0; a < 4; a++)
+        for (int c = 0; c < 4; c++) { x[0][c] = fx * P[8 + c] - fz * P[c]; x[1][c] = fy * P[8 + c] - fz * P[4 + c]; }
+        // rotate each new row into R: column c of the row is annihilated against R[c][c]
 #pragma unroll
-            for (int c = a; c < 4; c++) M[e++] += ra[a] * ra[c] + rb[a] * rb[c];
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                if (x[r][c] != 0.0) {
+                    const double rr = sqrt(G[c][c] * G[c][c] + x[r][c] * x[r][c]);
+                    const double inv = 1.0 / rr, cs = G[c][c] * inv, sn = x[r][c] * inv;
+                    G[c][c] = rr;
+#pragma unroll
+                    for (int e = c + 1; e < 4; e++) { const double g = G[c][e], y = x[r][e]; G[c][e] = cs * g + sn * y; x[r][e] = cs * y - sn * g; }
+                }
     }
-    // cyclic Jacobi on the symmetric 4x4 (static indices only: everything stays in registers)
-    double A[4][4], V[4][4];
-    {
-        int e = 0;
+    // one-sided Jacobi on the columns of R: a pair is rotated until it is orthogonal to 4 u relative to its norms
+    double V[4][4];
 #pragma unroll
-        for (int a = 0; a < 4; a++)
+    for (int a = 0; a < 4; a++)
 #pragma unroll
-            for (int c = a; c < 4; c++) { A[a][c] = M[e]; A[c][a] = M[e]; e++; }
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) V[a][c] = a == c ? 1.0 : 0.0;
-    }
+        for (int c = 0; c < 4; c++) V[a][c] = a == c ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 30; sweep++) {
-        double off = 0, dg = 0;
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            dg += A[a][a] * A[a][a];
-#pragma unroll
-            for (int c = a + 1; c < 4; c++) off += A[a][c] * A[a][c];
-        }
-        if (off <= 1e-32 * dg || off == 0.0) break;
+        bool rotated = false;
 #pragma unroll
         for (int p = 0; p < 3; p++)
 #pragma unroll
             for (int q = p + 1; q < 4; q++) {
-                const double apq = A[p][q];
-                if (apq != 0.0) {
-                    const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                double app = 0, aqq = 0, apq = 0;
+#pragma unroll
+                for (int r = 0; r < 4; r++) { app += G[r][p] * G[r][p]; aqq += G[r][q] * G[r][q]; apq += G[r][p] * G[r][q]; }
+                if (apq != 0.0 && fabs(apq) > 0x1p-51 * sqrt(app * aqq)) {
+                    rotated = true;
+                    const double theta = (aqq - app) / (2.0 * apq);
                     const double tq = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
                     const double c = 1.0 / sqrt(tq * tq + 1.0), sn = tq * c;
 #pragma unroll
-                    for (int r = 0; r < 4; r++) { const double akp = A[r][p], akq = A[r][q]; A[r][p] = c * akp - sn * akq; A[r][q] = sn * akp + c * akq; }
+                    for (int r = 0; r < 4; r++) { const double gp = G[r][p], gq = G[r][q]; G[r][p] = c * gp - sn * gq; G[r][q] = sn * gp + c * gq; }
 #pragma unroll
-                    for (int r = 0; r < 4; r++) { const double apk = A[p][r], aqk = A[q][r]; A[p][r] = c * apk - sn * aqk; A[q][r] = sn * apk + c * aqk; }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) { const double vkp = V[r][p], vkq = V[r][q]; V[r][p] = c * vkp - sn * vkq; V[r][q] = sn * vkp + c * vkq; }
+                    for (int r = 0; r < 4; r++) { const double vp = V[r][p], vq = V[r][q]; V[r][p] = c * vp - sn * vq; V[r][q] = sn * vp + c * vq; }
                 }
             }
+        if (!rotated) break;
     }
-    double best = A[0][0], v2 = V[2][0], v3 = V[3][0];
+    double best = 0, v2 = 0, v3 = 0;
 #pragma unroll
-    for (int c = 1; c < 4; c++) if (A[c][c] < best) { best = A[c][c]; v2 = V[2][c]; v3 = V[3][c]; }
+    for (int c = 0; c < 4; c++) {
+        double nn = 0;
+#pragma unroll
+        for (int r = 0; r < 4; r++) nn += G[r][c] * G[r][c];
+        if (c == 0 || nn < best) { best = nn; v2 = V[2][c]; v3 = V[3][c]; }
+    }
     double dep = v2 / v3;
     if (dep < 0.1 || dep > 8.0) dep = d.init_depth;
     d.depth[l] = dep;

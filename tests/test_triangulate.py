@@ -73,7 +73,7 @@ def test_gpu_triangulate_matches_oracle(oracle, n_frames, n_vo):
         b.triangulate(ws)
         for w, o in zip(ws, ref):
             a, e = np.array(w.lm_depth[: w.L]), np.array(o.lm_depth[: o.L])
-            # Gram-matrix eigenvector on the GPU vs one-sided Jacobi SVD in the oracle: 1e-7 relative on the depth
+            # QR + one-sided Jacobi on the GPU vs one-sided Jacobi SVD in the oracle (against 40 digits: tests/test_gpu_prep_highprec.py)
             assert np.abs(a / e - 1).max() < 1e-7, np.abs(a / e - 1).max()
     finally:
         b.close()
