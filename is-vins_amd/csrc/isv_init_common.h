@@ -11,7 +11,8 @@
  *   isv_excitation_var    Estimator::checkIMUExcitation's var (src/estimator.cpp:213-238), the first stage of both kernels
  *   rp_*                  the relative-pose RANSAC (isv_relpose.h): OpenCV 3.2's cv::RNG, RANSACPointSetRegistrator's
  *                         getSubset and RANSACUpdateNumIters, fundam.cpp's run7Point / computeError, cv::solveCubic,
- *                         cvTriangulatePoints and the reference's own decomposeEssentialMat / recoverPose cheirality test
+ *                         cvTriangulatePoints (rp_triangulate, which the rotation calibration's testTriangulation shares:
+ *                         isv_exrot.h) and the reference's own decomposeEssentialMat / recoverPose cheirality test
  *                         (src/initial/solve_5pts.cpp).  Restated from the published OpenCV 3.2 sources; the restatement pins
  *                         the GPU, not the reference.
  */
@@ -364,11 +365,10 @@ ISV_HD void rp_decompose(const double *E, double *P) {
         }
 }
 
-/* recoverPose's cheirality test of one correspondence against camera P (3 x 4, the other is [I | 0]): cvTriangulatePoints'
- * 6 x 4 system (three rows per view), its last right singular vector (Q X Y Z W), then Z W > 0, Z / W < dist and
- * 0 < (P Q / W).z < dist.  Deviation: the right singular vectors come from a Householder QR of the 6 x 4 system and
- * svd_jacobi of its 4 x 4 R factor (as Eigen's QR-preconditioned JacobiSVD), not OpenCV's one-sided SVD. */
-ISV_HD int rp_cheirality(const double *P, double x0, double y0, double x1, double y1) {
+/* cvTriangulatePoints of one correspondence against camera P (3 x 4, the other is [I | 0]): the 6 x 4 system (three rows per
+ * view) and its last right singular vector Q = (X Y Z W).  Deviation: the right singular vectors come from a Householder QR of
+ * the 6 x 4 system and svd_jacobi of its 4 x 4 R factor (as Eigen's QR-preconditioned JacobiSVD), not OpenCV's one-sided SVD. */
+ISV_HD void rp_triangulate(const double *P, double x0, double y0, double x1, double y1, double *Q) {
     const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     double A[24], Rm[16], w[4], V[16];
     for (int j = 0; j < 2; j++) {
@@ -401,7 +401,15 @@ ISV_HD int rp_cheirality(const double *P, double x0, double y0, double x1, doubl
     }
     for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) Rm[a * 4 + b] = b >= a ? A[a * 4 + b] : 0.0;
     svd_jacobi(4, Rm, w, 0, V);
-    const double X = V[3], Y = V[7], Z = V[11], Wh = V[15];
+    Q[0] = V[3]; Q[1] = V[7]; Q[2] = V[11]; Q[3] = V[15];
+}
+
+/* recoverPose's cheirality test of one correspondence against camera P: the triangulated Q, then Z W > 0, Z / W < dist and
+ * 0 < (P Q / W).z < dist */
+ISV_HD int rp_cheirality(const double *P, double x0, double y0, double x1, double y1) {
+    double Q[4];
+    rp_triangulate(P, x0, y0, x1, y1, Q);
+    const double X = Q[0], Y = Q[1], Z = Q[2], Wh = Q[3];
     const double dist = 50.0;
     int ok = Z * Wh > 0;
     const double Xn = X / Wh, Yn = Y / Wh, Zn = Z / Wh, Wn = Wh / Wh;

@@ -4,7 +4,8 @@
 // isv_reject.h, shared with the CPU restatement tests/native/isv_rej_oracle.c).  A rejector is bound to a tracker handle for its
 // device, stream and camera.
 //
-// k_rej_f: a lane per point lifts both sides into LDS as one float4 (x0 y0 x1 y1) in point order (J1).  From 15 points on the RANSAC
+// k_rej_f: a lane per point lifts both sides into LDS as one float4 (x0 y0 x1 y1) in point order (J1).  The estimator is rej_estimate
+// (isv_reject.h), which the rotation calibration's kernel calls too (isv_exrot.hip).  From 15 points on the RANSAC
 // runs as k_relpose's does (isv_relpose.hip), speculatively in chunks of up to 64 hypotheses: the subsets do not depend on the
 // models, so lane 0 draws the next chunk's subsets from the serial RNG stream (J6), each lane solves one 7-point system and counts
 // the inliers of its <= 3 models over the LDS points, and lane 0 then replays the serial loop over the chunk in iteration order, with
@@ -25,27 +26,19 @@
 
 namespace {
 
-constexpr int kLanes = 64;
+constexpr int kLanes = kRejLanes;
 
 struct RejParams {
     PinholeCam cam;
     double focal, thresh;
 };
 
-enum { SH_CNT = 0, SH_MORE, SH_KEPT, SH_END };
-
 }  // namespace
 
 __global__ void __launch_bounds__(kLanes) k_rej_f(const RejHdr *__restrict__ hdrs, const float *__restrict__ pts, isv_rej_result_t *__restrict__ results,
                                                   uint8_t *__restrict__ status, const RejParams P) {
     extern __shared__ float4 Lp[];             // correspondence (x0 y0 x1 y1) = (m1, m2), float32 (J1)
-    __shared__ int16_t Lsub[kLanes][7];        // the chunk's subsets
-    __shared__ double LF[kLanes][27];          // their models
-    __shared__ double Lmed[kLanes][3];         // LMedS: their medians
-    __shared__ int Lnm[kLanes], Lgood[kLanes][3];
-    __shared__ double Lbest[9];
-    __shared__ float Lbound;                   // the kept model's float32 inlier bound
-    __shared__ int sh[SH_END];
+    __shared__ RejEstLds E;                    // the estimator's chunk, the kept model and its float32 inlier bound
 
     const RejHdr H = hdrs[blockIdx.x];
     isv_rej_result_t *res = results + blockIdx.x;
@@ -66,91 +59,11 @@ __global__ void __launch_bounds__(kLanes) k_rej_f(const RejHdr *__restrict__ hdr
     }
     __syncthreads();
 
-    const bool lmeds = count < ISV_REJ_RANSAC_MIN;     // J3
-    const float tf = (float)(P.thresh * P.thresh);     // J2
-    uint64_t rng = ~0ull;                      // lane 0's: RNG((uint64)-1), fresh per call (J6)
-    int iter = 0, niters = lmeds && t == 0 ? rej_lmeds_niters() : RP_MAX_ITERS, max_good = 0, kept = 0;   // lane 0's
-    double min_median = DBL_MAX;               // lane 0's
-    for (;;) {
-        if (t == 0) {
-            const int cnt = niters - iter < kLanes ? niters - iter : kLanes;
-            for (int h = 0; h < cnt; h++) {
-                int idx[7];
-                rp_subset(&rng, count, idx);
-                for (int k = 0; k < 7; k++) Lsub[h][k] = (int16_t)idx[k];
-            }
-            sh[SH_CNT] = cnt;
-        }
-        __syncthreads();
-        const int cnt = sh[SH_CNT];
-        if (t < cnt) {
-            double p[28];
-            for (int k = 0; k < 7; k++) {
-                const float4 v = Lp[Lsub[t][k]];
-                p[4 * k] = v.x; p[4 * k + 1] = v.y; p[4 * k + 2] = v.z; p[4 * k + 3] = v.w;
-            }
-            int nm = rp_run7point(p, LF[t]);
-            nm = nm < 1 || nm > 3 ? 0 : nm;
-            Lnm[t] = nm;
-            for (int m = 0; m < nm; m++) {
-                double F[9];
-                for (int k = 0; k < 9; k++) F[k] = LF[t][9 * m + k];
-                if (lmeds) {
-                    float e[REJ_MAX_MODEL_PTS];
-                    for (int j = 0; j < count; j++) {
-                        const float4 v = Lp[j];
-                        e[j] = (float)rp_fm_error(F, v.x, v.y, v.z, v.w);
-                    }
-                    Lmed[t][m] = rej_median(e, count);              // J4
-                } else {
-                    int g = 0;
-                    for (int j = 0; j < count; j++) {
-                        const float4 v = Lp[j];
-                        g += (float)rp_fm_error(F, v.x, v.y, v.z, v.w) <= tf;   // J2
-                    }
-                    Lgood[t][m] = g;
-                }
-            }
-        }
-        __syncthreads();
-        if (t == 0) {   // the serial loop over this chunk, in iteration order
-            for (int h = 0; h < cnt && iter < niters; h++, iter++)
-                for (int m = 0; m < Lnm[h]; m++) {
-                    if (lmeds) {
-                        const double median = Lmed[h][m];
-                        if (median < min_median) {
-                            min_median = median;
-                            for (int k = 0; k < 9; k++) Lbest[k] = LF[h][9 * m + k];
-                            kept = 1;
-                        }
-                    } else {
-                        const int g = Lgood[h][m];
-                        if (g > (max_good > 6 ? max_good : 6)) {
-                            for (int k = 0; k < 9; k++) Lbest[k] = LF[h][9 * m + k];
-                            max_good = g;
-                            kept = 1;
-                            niters = rp_update_num_iters(RP_CONFIDENCE, (double)(count - g) / count, 7, niters);
-                        }
-                    }
-                }
-            sh[SH_MORE] = iter < niters;
-        }
-        __syncthreads();
-        if (!sh[SH_MORE]) break;
-    }
-    if (t == 0) {
-        sh[SH_KEPT] = kept;
-        float bound = tf;
-        if (lmeds && kept) {
-            const double sigma = rej_sigma(count, min_median);
-            bound = (float)(sigma * sigma);
-        }
-        Lbound = bound;
-    }
-    __syncthreads();
+    rej_estimate(Lp, count, P.thresh, E);      // J2, J3, J6
+    const bool lmeds = count < ISV_REJ_RANSAC_MIN;
     // ---- the kept model's mask, a lane per point; nothing kept: every point is rejected (J5) ----
-    const bool any = sh[SH_KEPT] != 0;
-    const float bound = Lbound;
+    const bool any = E.kept != 0;
+    const float bound = E.bound;
     int n_kept = 0;
     for (int b = 0; b < count; b += kLanes) {
         const int j = b + t;
@@ -158,15 +71,15 @@ __global__ void __launch_bounds__(kLanes) k_rej_f(const RejHdr *__restrict__ hdr
         if (j < count) {
             if (any) {
                 const float4 v = Lp[j];
-                in = (float)rp_fm_error(Lbest, v.x, v.y, v.z, v.w) <= bound;
+                in = (float)rp_fm_error(E.best, v.x, v.y, v.z, v.w) <= bound;
             }
             st[j] = in ? 1 : 0;
         }
         n_kept += __popcll(__ballot(in));
     }
     if (t == 0)
-        *res = isv_rej_result_t{ISV_TRK_OK, count, n_kept, lmeds ? ISV_REJ_LMEDS : ISV_REJ_RANSAC, lmeds ? niters : iter,
-                                any ? (lmeds ? n_kept : max_good) : 0, lmeds && any ? min_median : -1.0};
+        *res = isv_rej_result_t{ISV_TRK_OK, count, n_kept, lmeds ? ISV_REJ_LMEDS : ISV_REJ_RANSAC, E.iters,
+                                any ? (lmeds ? n_kept : E.max_good) : 0, lmeds && any ? E.min_median : -1.0};
 }
 
 extern "C" const char *isv_rej_last_error(const isv_rej_t *h) { return h ? h->err.c_str() : "null handle"; }
