@@ -128,7 +128,8 @@ struct DevBatch {
     const int32_t *seq_hdr;             // device-resident sequences: the frame headers [B][8]; header word 0 < 0 = this window has NO FRAME this step (ISV_SEQ_IDLE):
                                         // nothing is slid, appended, solved or written back for it.  null on the upload path
     double *st_ws;                      // [B][build_solve_st_ws_doubles(N)] = [324 N] (N <= 11) or [324 N + ytot] k_build_solve_st: L_i^-1 | C_i' of the chain nodes between elimination and back-substitution | Y_i' (long windows only: their tile wavefronts read it) | the prescaled init blocks of every node; null: the handle runs k_build_solve_sb
-    int32_t split_cap, _pad4;            // groups a window's rank-1 downdates may be split into on this handle (from max_batch at creation; 1: never split)
+    int32_t split_cap, r1_dense;         // groups a window's rank-1 downdates may be split into on this handle (from max_batch at creation; 1: never split);
+                                        // r1_dense (ISV_R1_DENSE, read at creation): the downdates' dense MFMA loop in place of the per-tile compacted one (isv_rank1.h; same bits)
     double *cs_ws;                      // [B][sb_cs_doubles(N)] hand-over of the split solve (k_build_solve_sb MODE 1 -> MODE 2: isv_build_solve_sb.hip); null: the handle solves in one launch
     double *r1_part;                    // [split_cap_B][ISV_SPLIT_MAX_GROUPS][tiles * 256] raw accumulator tiles of the split rank-1 downdates (k_schur_split -> k_schur_fold); null: no split on this handle
     double *Tvis;                       // [B][tvis_sz] reprojection part of the reduced system (6x6 pose corners), hd, g, bs

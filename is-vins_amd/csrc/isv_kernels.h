@@ -58,6 +58,7 @@ struct SolverHost {
     bool marg_split = false;          // project, whatever the batch size (default: k_marg_bwd<3>, one launch of four wavefronts per window); all bitwise equal (tested)
     bool tail_one_wave = false;       // ISV_TAIL_ONE_WAVE (A/B and test hook): the one-wavefront tail -- k_finalize<64> + k_marg_clear, and MargBackward as
                                       // k_marg_bwd<2> (max_batch > 3 n_cus) or build / k_marg_jacobi / project -- in place of k_finalize<256> and k_marg_bwd<3> (same bits)
+    bool r1_dense = false;            // ISV_R1_DENSE (A/B and test hook): k_rank1_mfma's dense MFMA loop, every landmark through every tile (DevBatch::r1_dense; same bits)
     bool no_update = false;           // ISV_DEBUG_NO_UPDATE (sensitivity study, tests/test_sequence_long.py; the oracle has the same
                                       // hook): skip the update() of the prior factors' pseudo-measurements after the solve
                                       // (src/estimator.cpp:1133-1144).  NOT the reference's behaviour.
@@ -77,6 +78,9 @@ __global__ void k_triangulate(DevBatch d);
 template <bool EX, int LGW> __global__ void k_lin_gram(DevBatch d);     // EX: the extrinsic is estimated (J_ex, one more block row)
 size_t lin_gram_lds_bytes(int N, bool partials_in_lds, bool ex, int waves, int lcap);
 #define ISV_LDS_PER_CU ((size_t)160 * 1024)
+// bytes of the wave-private landmark lists of k_rank1_mfma's compacted downdates (isv_rank1.h): 64 per output-tile slot, and
+// wavefronts x tiles per wavefront <= tiles + 3 slots for nt 16-column blocks
+__host__ __device__ inline size_t rank1_list_bytes(int nt) { return (size_t)(nt * (nt + 1) / 2 + 3) * 64; }
 template <int NT, int TPW> __global__ void k_schur_split(DevBatch d, int Gs, int GrMax);
 template <int NT, int TPW> __global__ void k_rank1_split(DevBatch d, int GrMax);
 __global__ void k_schur_fold(DevBatch d, int GrMax, int NT, int from_partials);

@@ -13,7 +13,8 @@ __host__ __device__ inline int tvis_col(int a, int N) { return 36 * (a * N - a *
 // does not see it) with g_l appended in column 6N.  One wavefront per 16x16 output tile (lower triangle,
 // zero padded to 16s), v_mfma_f64_16x16x4: A = c_l * P[l][16I + i] for 4 landmarks, B = P[l][16J + j].
 // The dense panels multiply structural zeros, but one MFMA replaces ~1000 scalar lane-FMAs with their
-// address arithmetic (the scalar sweep was issue bound).  Row 6N of the product is sum c_l g_l w_l = -bs,
+// address arithmetic (the scalar sweep was issue bound); each tile wavefront walks only the landmarks of a pass that touch its
+// row and column block (rank1_touches and the compacted loop below).  Row 6N of the product is sum c_l g_l w_l = -bs,
 // the reduced right-hand side.  The packed w vectors (HBM) are expanded to panel rows in LDS, 64 landmarks
 // per pass; the loads of the next pass are in flight while the current one is multiplied.
 typedef double double4v __attribute__((ext_vector_type(4)));
@@ -34,6 +35,13 @@ __host__ __device__ inline int schur_split_groups(int P, int cap) {
     if (g > cap) g = cap;
     return (P >= ISV_SPLIT_MIN_PASSES && g >= 2) ? g : 1;
 }
+// Does the panel row of a landmark (metadata word m0: host h = m0 & 255, track length k = (m0 >> 8) & 255) have a non-zero in the
+// 16-column block Bk?  Its own track's columns [6h, 6(h + k)), the rhs column 6N, and with the extrinsic estimated (Nr < N) the
+// pseudo-frame's columns [6 Nr, 6N) of every landmark.  A superset of the non-zeros: a block covered in part is touched.
+__host__ __device__ inline bool rank1_touches(unsigned m0, int Bk, int N, int Nr) {
+    const int h6 = 6 * (int)(m0 & 255), k6 = 6 * (int)((m0 >> 8) & 255), c0 = 16 * Bk, c1 = c0 + 16;
+    return (h6 < c1 && h6 + k6 > c0) || Bk == (6 * N) / 16 || (Nr < N && 6 * Nr < c1 && 6 * N > c0);
+}
 template <int NT, int TPW, int R1_CHUNK, int MINW, bool EX, bool SPLIT = false>
 // (NT = 5, the benchmark's 11 frames: 15 wavefronts per workgroup, and two workgroups share a CU only at <= 64 VGPRs)
 __device__ __forceinline__ void rank1_body(DevBatch &d, const int grp = 0, const int GrMax = 1) {
@@ -41,7 +49,7 @@ __device__ __forceinline__ void rank1_body(DevBatch &d, const int grp = 0, const
     constexpr int ld = 16 * NT, nthr = 64 * nwaves;
     constexpr int R1_PF = (R1_CHUNK * ld + nthr - 1) / nthr;   // panel elements per thread and pass
     extern __shared__ __align__(16) double lds[];
-    const int w = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int w = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // (wave-uniform: the tile indices stay in scalar registers)
     const SolveState &st = d.st[w];
     if (st.termination != ISV_TERM_RUNNING || !st.need_linearize) return;
     const int N = d.N, n6 = 6 * N;
@@ -59,6 +67,8 @@ __device__ __forceinline__ void rank1_body(DevBatch &d, const int grp = 0, const
     double *sW = lds;                      // [R1_CHUNK][ld + 4]
     double2 *sCG = (double2 *)(lds + R1_CHUNK * lds_ld);       // [max_lm] {c_l, g_l}
     unsigned *sM = (unsigned *)(sCG + d.max_lm);               // [max_lm] landmark metadata
+    unsigned char *sL = (unsigned char *)(sM + d.max_lm);      // [nwaves * TPW][64] per output tile: the rows of the pass that touch it (rank1_list_bytes)
+    const int NrT = EX ? d.Nr : d.N;                           // (the pseudo-frame's columns exist only with the extrinsic estimated)
     const int fw0 = d.f_off[w];
     double *out = d.Tvis + (size_t)w * d.tvis_sz;
     const int tail = 36 * (N * (N + 1) / 2);
@@ -189,14 +199,55 @@ __device__ __forceinline__ void rank1_body(DevBatch &d, const int grp = 0, const
         R1STAMP(12);
         if (lb + R1_CHUNK < l1) fetch(lb + R1_CHUNK);      // in flight during the MFMAs below
         R1STAMP(13);
+        if (d.r1_dense) {                                  // ISV_R1_DENSE (A/B and test hook): every landmark of the pass through every tile
 #pragma unroll 4
-        for (int k4 = 0; k4 < R1_CHUNK; k4 += 4) {
-            const int l = k4 + kq, lg = lb - l0 + l;
-            const double cl = lg < Lw ? sCG[lg].x : 0.0;
+            for (int k4 = 0; k4 < R1_CHUNK; k4 += 4) {
+                const int l = k4 + kq, lg = lb - l0 + l;
+                const double cl = lg < Lw ? sCG[lg].x : 0.0;
+#pragma unroll
+                for (int j = 0; j < TPW; j++) {
+                    const double av = sW[l * lds_ld + 16 * TI[j] + i] * cl, bv = sW[l * lds_ld + 16 * TJ[j] + i];
+                    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+        } else {
+            // A tile wavefront walks only the landmarks of the pass whose panel rows are non-zero in BOTH its row block and its column
+            // block, in landmark order, four per MFMA: what is left out are products with an exact zero, and an output element
+            // receives its non-zero products in the dense loop's order (the same bits; tests/test_gpu_rank1_compact.py).  lane =
+            // landmark of the pass; the set lanes write their row at their rank into the tile's wave-private list.
+            const int lp = lb - l0 + lane;
+            const bool lv = lane < R1_CHUNK && lp < Lw;
+            const unsigned mp = sM[lv ? lp : 0];
 #pragma unroll
             for (int j = 0; j < TPW; j++) {
-                const double av = sW[l * lds_ld + 16 * TI[j] + i] * cl, bv = sW[l * lds_ld + 16 * TJ[j] + i];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[j], 0, 0, 0);
+                unsigned char *lst = sL + (wv * TPW + j) * 64;
+                const unsigned long long mask = __ballot(lv && rank1_touches(mp, TI[j], N, NrT) && rank1_touches(mp, TJ[j], N, NrT));
+                if ((mask >> lane) & 1ull)
+                    lst[__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u))] = (unsigned char)lane;
+                __builtin_amdgcn_wave_barrier();           // (one wavefront, LDS in program order: the list is read by other lanes below)
+                const int cnt = __popcll(mask);            // wave-uniform
+                // four whole steps at a time (the dense loop's `#pragma unroll 4`, by hand: the run-time trip count is not unrolled
+                // by the pragma): the dependent row-index reads of a group are issued together, ahead of its MFMAs
+                int e0 = 0;
+                for (; e0 + 16 <= cnt; e0 += 16) {
+                    int l[4]; double cl[4], pa[4], pb[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) l[u] = lst[e0 + 4 * u + kq];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        cl[u] = sCG[lb - l0 + l[u]].x; pa[u] = sW[l[u] * lds_ld + 16 * TI[j] + i]; pb[u] = sW[l[u] * lds_ld + 16 * TJ[j] + i];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[u] * cl[u], pb[u], acc[j], 0, 0, 0);
+                }
+                for (; e0 < cnt; e0 += 4) {
+                    const bool on = e0 + kq < cnt;
+                    const int lr = lst[e0 + kq];           // (always inside the tile's 64 bytes; an entry past cnt is stale: not used)
+                    const int l = on ? lr : 0;
+                    const double cl = sCG[lb - l0 + l].x, pa = sW[l * lds_ld + 16 * TI[j] + i], pb = sW[l * lds_ld + 16 * TJ[j] + i];
+                    const double av = on ? pa * cl : 0.0, bv = on ? pb : 0.0;
+                    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[j], 0, 0, 0);
+                }
             }
         }
         R1STAMP(14);

@@ -315,7 +315,9 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     const size_t nblkT = (size_t)d.N * (d.N + 1) / 2 * 225;
     // LDS-resident fast path: the structure-aware solve (two windows per CU up to N = 11, one beyond), the pair
     // partials of k_sweep_mfma and the panel + landmark tables of k_rank1_mfma must fit the 160 KB of a CU
-    const size_t lds_r1 = (64 * (size_t)(d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
+    // (+ the compacted downdates' landmark lists, 64 bytes per output tile: isv_rank1.h -- added below, where they still fit a CU;
+    //  whether the handle takes the LDS path is decided WITHOUT them, as before: the dense loop gives the same bits)
+    size_t lds_r1 = (64 * (size_t)(d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
     const size_t n_pairs = (size_t)d.N * (d.N - 1) / 2;
     const bool sw_global = n_pairs * 84 * sizeof(double) > 40 * 1024;      // partials too big to share a CU's LDS four ways
     const size_t lds_sw = (n_pairs * 84 + (n_pairs + 2) / 2 + 1) * sizeof(double);       // (the LDS variant's size; the global one needs less)
@@ -334,6 +336,11 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     hc.no_update = getenv("ISV_DEBUG_NO_UPDATE") != nullptr; hc.no_pose_dogleg = getenv("ISV_NO_POSE_DOGLEG") != nullptr;
     hc.marg_one_kernel = getenv("ISV_MARG_ONE_KERNEL") != nullptr; hc.marg_split = getenv("ISV_MARG_SPLIT") != nullptr;
     hc.tail_one_wave = getenv("ISV_TAIL_ONE_WAVE") != nullptr;
+    // the rank-1 downdates' per-tile landmark lists, unless ISV_R1_DENSE asks for the dense loop or the lists do not fit the CU's LDS
+    // beside the panel and the landmark tables (max_landmarks near 4000 at 20 frames): the dense loop then, on the same LDS as before
+    hc.r1_dense = getenv("ISV_R1_DENSE") != nullptr || lds_r1 + rank1_list_bytes(d.wd_ld / 16) > ISV_LDS_PER_CU;
+    d.r1_dense = hc.r1_dense ? 1 : 0;
+    if (!hc.r1_dense) lds_r1 += rank1_list_bytes(d.wd_ld / 16);
     int dev0_ = 0;
     HCHK(hipGetDevice(&dev0_));
     if (hipDeviceGetAttribute(&hc.n_cus, hipDeviceAttributeMultiprocessorCount, dev0_) != hipSuccess) { (void)hipGetLastError(); hc.n_cus = 0; }
