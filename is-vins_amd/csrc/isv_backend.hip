@@ -505,10 +505,13 @@ extern "C" int isv_batch_upload(isv_backend_t *h, int32_t n, isv_window_t *const
     // gives the same bits alone and inside any batch of such windows.  (a free extrinsic only exists in k_lin_gram<true>;
     // ISV_LEGACY_VISUAL: test / measurement hook for the unfused pair)
     // k_lin_gram also stages the window's inverse depths and host points in LDS (32 B per landmark): the longest window must fit
-    d.lg_lcap = (int32_t)((Lmax + 31) / 32 * 32);
-    const bool lg_fits = lin_gram_lds_bytes(c.n_frames, true, c.estimate_extrinsic != 0, LG_WAVES, d.lg_lcap) <= ISV_LDS_PER_CU;
-    if (c.estimate_extrinsic && !lg_fits) { h->err = "estimate_extrinsic = 1: a window has more landmarks than k_lin_gram<true> can stage in LDS"; return ISV_ERR_CAPACITY; }
-    d.fused_visual = (c.estimate_extrinsic || !(h->hc.legacy_visual || Fmax > ISV_FUSED_MAX_FACTORS || !lg_fits)) ? 1 : 0;
+    // (the rule: plan_upload, isv_solve_plan.h)
+    UploadShape up;
+    up.B = n; up.Ftot = q.F; up.Fmax = Fmax; up.Lmax = Lmax; up.n_tiles = (int)q.T; up.est_ex = c.estimate_extrinsic;
+    const UploadPlan uplan = isv_solver_plan_upload(h->hc, up);
+    d.lg_lcap = uplan.lg_lcap;
+    if (c.estimate_extrinsic && !uplan.fused_visual) { h->err = "estimate_extrinsic = 1: a window has more landmarks than k_lin_gram<true> can stage in LDS"; return ISV_ERR_CAPACITY; }
+    d.fused_visual = uplan.fused_visual ? 1 : 0;
     // send the rest
     if (copy_failed.load()) { h->err = "isv_batch_upload: host-to-device copy failed"; return ISV_ERR_DEVICE; }
     switch (plan) {

@@ -53,7 +53,7 @@ struct isv_backend {
     std::vector<hipEvent_t> prof_ev;      // [max_iter][ISV_PROF_FAMILIES][2]
     int prof_valid = 0;
     DevBatch d{};                 // device pointers
-    SolverHost hc;                // device figures + environment hooks, read once at creation
+    SolverHost hc;                // the solver's environment hooks, device figures, handle plan and kernel table, set at creation; the resident upload's sizes
     std::vector<void *> allocs;
     // capacities
     size_t capB = 0, capL = 0, capF = 0, capTiles = 0;

@@ -10,7 +10,7 @@
 // Data layout: the reduced matrix T (15N x 15N, symmetric) is kept as the lower block triangle of
 // 15x15 blocks (one block row per frame), N(N+1)/2 * 225 doubles, in an L2-resident global scratch
 // (d.Tglob).  This kernel serves the handles the LDS-resident solves (isv_build_solve_sb.hip,
-// isv_build_solve_st.hip) do not take (d.lds_T == 0: windows beyond 20 frames, see isv_solver_alloc).
+// isv_build_solve_st.hip) do not take (d.lds_T == 0: windows beyond 20 frames, see plan_handle, isv_solve_plan.h).
 // Reprojection strips are streamed through LDS in chunks of <= 64 factors (whole landmarks).
 // Accumulation is OWNER-COMPUTES: wavefront `a` owns block column `a` (frame a), so every T entry is
 // summed by one lane in landmark order -- bitwise reproducible, no atomics.

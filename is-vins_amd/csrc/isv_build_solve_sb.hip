@@ -65,7 +65,7 @@ DEV int sbt(int I, int J, int N) { return (I == J ? I : N + J) * 36; }
 //   MODE 2 (k "pose", main stream, after k_rank1_mfma and the join): T_pp = s s (V + S_nv - Y'Y'^T) + mu D^2, pose Cholesky, the back-substitutions
 //          and the outputs.  A failed factorisation on either side (mu retry) falls back to the one-launch path inside this kernel.
 // The split sums the same products in a different order than MODE 0 (the row scaling is applied after the chain instead of before): results agree to
-// rounding; which one a handle runs is decided by its max_batch (SolverHost::chain_split), never by the uploaded batch.
+// rounding; which one a handle runs is decided by its max_batch (HandlePlan::chain_split, isv_solve_plan.h), never by the uploaded batch.
 __host__ __device__ inline size_t sb_cs_doubles(int N) {
     return (2 * (size_t)N - 1) * 36 + (size_t)N * (N + 1) / 2 * 36 + 162 * (size_t)N + chain_fill_doubles<size_t>(N) + 3 * 15 * (size_t)N + 6 * (size_t)N + 8;
 }
@@ -1215,7 +1215,7 @@ __global__ __launch_bounds__(LS, 2) void k_pose_dogleg(DevBatch d) {
     __syncthreads();                                  // candidate states, per-factor costs and model pieces of this window are written
     step_control_body<true, EX>(d, blockIdx.x, threadIdx.x, lds, red, s_accept);
 }
-// (every form the solver's per-handle kernel table can name: isv_solver_alloc)
+// (every form the solver's per-handle kernel table can name: isv_solver_kernel)
 template __global__ void k_pose_dogleg<false, 11, false>(DevBatch);
 template __global__ void k_pose_dogleg<false, 0, false>(DevBatch);
 template __global__ void k_pose_dogleg<false, 0, true>(DevBatch);

@@ -9,16 +9,11 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/isvins_backend.h"
+#include "isv_solve_plan.h"      // ISV_SPLIT_*, ISV_FUSED_MAX_FACTORS, ISV_SWEEP_WAVES: constants of the launch rules
 
 #define ISV_TILE 64            // reprojection factors per wavefront tile
 #define ISV_MAX_FRAMES 32
 #define ISV_MARG_WS 1408             // doubles per window: Lp @0 (441), Jr @448 (441), V @896 (441), eigenvalues @1344 (21)
-#define ISV_SPLIT_MAX_GROUPS 32       // workgroups one window's rank-1 downdates are split over (k_schur_split)
-#ifndef ISV_SPLIT_MIN_PASSES
-#define ISV_SPLIT_MIN_PASSES 4        // ... when it has at least this many 64-landmark passes (> 192 landmarks; measured on ONE 18-frame
-                                      // window of 300 landmarks: 2.66 ms with 8, 2.52 ms with 4; 11 frames: 1.94 either way)
-#endif
-#define ISV_FUSED_MAX_FACTORS 8192   // longest window (reprojection factors) the one-workgroup-per-window k_lin_gram takes
 #define ISV_IMU_IN 64          // packed IMU record (doubles)
 // offsets inside the packed IMU record
 #define IMU_DP 0
@@ -34,7 +29,6 @@
 #define IMU_DV_DBG 53
 
 // per-window prior strip layout (doubles): [se3: r6 J36][lin9: r9 J81][relpose k: r6 Ji36 Jj36]...[rollpitch m: r2 J12]
-#define ISV_SWEEP_WAVES 8
 #define PR_SE3 0
 #define PR_LIN9 42
 #define PR_REL0 132

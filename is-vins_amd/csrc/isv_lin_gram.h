@@ -9,7 +9,6 @@
 __host__ __device__ inline int tvis_col2(int a, int N) { return 36 * (a * N - a * (a - 1) / 2); }
 typedef double double4g __attribute__((ext_vector_type(4)));
 // LDS row of one factor: r(2) J_i(12) J_j(12) [+ J_ex(12) when the extrinsic is estimated] + 1 (odd stride)
-__host__ __device__ constexpr int lg_xld(bool ex) { return ex ? 39 : 27; }
 
 // LGW wavefronts per window: 4 for batches (158 VGPRs -> three workgroups per CU), 8 while every window has a CU of its own
 // (twice the wavefronts on the factor stream; which wavefront sums a pair group does not change the sums)

@@ -535,7 +535,6 @@ __global__ __launch_bounds__(256) void k_upload_build(DevBatch d, const int32_t 
     __syncthreads();
     build_pairs_stream(d, w, t, Lw, Fw, F0, d.Nr, lcap, ldsi);
 }
-size_t upload_build_lds_bytes(int N, int lcap) { return ((size_t)2 * lcap + 9 * ((size_t)N * (N - 1) / 2 + 1)) * sizeof(int32_t); }
 int isv_upload_build_enqueue(DevBatch &d, const int32_t *optr, const double *obs_raw, int lcap, hipStream_t st) {
     const size_t lds = upload_build_lds_bytes(d.Nr, lcap);
     int dev = 0;
@@ -762,9 +761,11 @@ extern "C" int isv_backend_seq_frame(isv_backend_t *h, int32_t n, const isv_seq_
     if (n_idle == n) { h->err = "seq_frame: no sequence has a frame"; return ISV_ERR_INVALID_ARG; }
     d.B = n; d.Ltot = (int32_t)L; d.Ftot = (int32_t)F; d.n_tiles = 0;
     d.seq_hdr = s.f_hdr;
-    d.lg_lcap = (int32_t)((Lmax + 31) / 32 * 32);
-    const bool lg_fits = lin_gram_lds_bytes(N, true, c.estimate_extrinsic != 0, LG_WAVES, d.lg_lcap) <= ISV_LDS_PER_CU;
-    if (!d.lds_T || Fmax > ISV_FUSED_MAX_FACTORS || !lg_fits || h->hc.legacy_visual || F > (size_t)4096 * n) {
+    UploadShape up;
+    up.B = n; up.Ftot = F; up.Fmax = Fmax; up.Lmax = Lmax; up.n_tiles = 0; up.est_ex = c.estimate_extrinsic; up.resident = 1;
+    const UploadPlan plan = isv_solver_plan_upload(h->hc, up);
+    d.lg_lcap = plan.lg_lcap;
+    if (!plan.fused_visual) {
         h->err = "device-resident sequences run the per-window kernels only (N <= 20, <= 8192 factors per window): use the upload path";
         return ISV_ERR_UNSUPPORTED;
     }
@@ -784,9 +785,8 @@ extern "C" int isv_backend_seq_frame(isv_backend_t *h, int32_t n, const isv_seq_
     hipLaunchKernelGGL(k_seq_slide, dim3(n), dim3(256), 0, st, d, s);
     hipLaunchKernelGGL(k_seq_append, dim3(n), dim3(256), 0, st, d, s);
     hipLaunchKernelGGL(k_imu_prep, dim3(2 * n), dim3(64), 0, st, d, s.imu_sel);
-    const int NP = N * (N - 1) / 2, lcap = c.max_landmarks > 1 ? c.max_landmarks : 1;
-    const size_t lds_build = ((size_t)2 * lcap + 9 * (size_t)(NP + 1)) * sizeof(int32_t);
-    hipLaunchKernelGGL(k_seq_build, dim3(n), dim3(256), lds_build, st, d, s, lcap);
+    const int lcap = c.max_landmarks > 1 ? c.max_landmarks : 1;
+    hipLaunchKernelGGL(k_seq_build, dim3(n), dim3(256), upload_build_lds_bytes(N, lcap), st, d, s, lcap);
     if (L) hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((L + 63) / 64)), dim3(64), 0, st, d);
     HIPCHK(h, hipGetLastError());
     memset(h->last_counts, 0, sizeof(h->last_counts));

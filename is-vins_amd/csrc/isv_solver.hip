@@ -270,34 +270,91 @@ hipError_t isv_raise_dynamic_lds(const void *fn, int device, size_t lds) {
     if (e == hipSuccess) cur = lds;
     return e;
 }
-// dynamic LDS of k_dogleg (candidate-point IMU / prior evaluation on the LDS path + the two tangent vectors) and of the step control
-static size_t dogleg_lds_bytes(const DevBatch &d) {
-    // + two 496-double staging rows for the IMU J^T J records of the model pieces and the tangent step (np)
-    // + the window's prior J^T J record (prior_H_sz) for the priors' model pieces
-    return (d.lds_T ? ((size_t)(d.N - 1) * 48 + (size_t)d.n_prior_slots * 16 + 992 + (size_t)d.np + (d.dg_stage_ph ? (size_t)d.prior_H_sz : 0)) * sizeof(double) + prior_lds_bytes(d.n_prior_slots, false) : 0) + 2 * (size_t)d.np * sizeof(double);
+// ---- the handle: environment, device, plan, allocations, kernel table ---------------------------------------------------------
+// every environment hook of the solver, read at handle creation
+static SolveEnv solve_env_read() {
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto tri = [](const char *name) { const char *v = getenv(name); return v ? (atoi(v) != 0 ? 1 : 0) : -1; };
+    SolveEnv e;
+    e.one_stream = on("ISV_ONE_STREAM"); e.split_control = on("ISV_SPLIT_CONTROL"); e.generic_n = on("ISV_GENERIC_N");
+    e.lg_batch_waves = on("ISV_LG_BATCH_WAVES"); e.debug_sw_global = on("ISV_DEBUG_SW_GLOBAL"); e.legacy_visual = on("ISV_LEGACY_VISUAL");
+    e.no_split = on("ISV_NO_SPLIT"); e.no_update = on("ISV_DEBUG_NO_UPDATE"); e.no_pose_dogleg = on("ISV_NO_POSE_DOGLEG");
+    e.marg_one_kernel = on("ISV_MARG_ONE_KERNEL"); e.marg_split = on("ISV_MARG_SPLIT"); e.tail_one_wave = on("ISV_TAIL_ONE_WAVE");
+    e.r1_dense = on("ISV_R1_DENSE"); e.debug_path = on("ISV_DEBUG_PATH");
+    e.solve_st = tri("ISV_SOLVE_ST"); e.chain_split = tri("ISV_CHAIN_SPLIT");
+    return e;
 }
-// the step control: candidate / current poses, the tangent step, and (when they fit) the per-landmark data its factor loop gathers
-// -- host point, candidate and current inverse depth, the landmark's step: 6 doubles each (d.ctl_stage_lm, set per enqueue)
-static size_t step_control_lds_bytes(const DevBatch &d) { return ((size_t)30 * d.N + 12 + (d.ctl_stage_lm ? 6 * (size_t)d.lg_lcap : 0)) * sizeof(double); }
-#define ISV_CTL_STAGE_MAX_BYTES ((size_t)36 * 1024)      // staged only while four workgroups still share a CU
 
-// the reduced-system kernels: N = 11 compiled in (unless ISV_GENERIC_N), else run-time N; BIG beyond 11 frames
-template <int MODE> static const void *solve_sb_kernel(int N, bool generic_n) {
-    if (N == 11 && !generic_n) return (const void *)k_build_solve_sb<false, 11, MODE>;
-    return N <= 11 ? (const void *)k_build_solve_sb<false, 0, MODE> : (const void *)k_build_solve_sb<true, 0, MODE>;
+// the instantiation behind a role's enum: the only place that names them
+template <int MODE> static const void *solve_sb_kernel(KernelInst i) {
+    return i == SB_N11 ? (const void *)k_build_solve_sb<false, 11, MODE> : i == SB_RT ? (const void *)k_build_solve_sb<false, 0, MODE> : (const void *)k_build_solve_sb<true, 0, MODE>;
 }
-// the landmark elimination's kernels for NT 16-column tiles: TPW tiles per wavefront, 64 * ceil(NT (NT + 1) / 2 / TPW) threads
-template <int NT> static void set_rank1_kernels(SolverKernel *k, bool ex, bool split, size_t lds_r1, size_t lds_sp) {
+// the landmark elimination's kernels for NT 16-column tiles: TPW tiles per wavefront (the plan's thread count follows the same rule)
+template <int NT> static const void *rank1_kernel(SolverRole r, bool ex) {
     constexpr int TPW = NT <= 5 ? 1 : NT <= 7 ? 2 : 3;
-    constexpr unsigned threads = 64 * ((NT * (NT + 1) / 2 + TPW - 1) / TPW);
-    k[KR_RANK1] = {ex ? (const void *)k_rank1_mfma<NT, TPW, 64, 1, true> : (const void *)k_rank1_mfma<NT, TPW, 64, 1, false>, threads, lds_r1};
-    if (split) {
-        k[KR_RANK1_SPLIT] = {(const void *)k_rank1_split<NT, TPW>, threads, lds_r1};
-        k[KR_SCHUR_SPLIT] = {(const void *)k_schur_split<NT, TPW>, threads, lds_sp};
+    if (r == KR_RANK1_SPLIT) return (const void *)k_rank1_split<NT, TPW>;
+    if (r == KR_SCHUR_SPLIT) return (const void *)k_schur_split<NT, TPW>;
+    return ex ? (const void *)k_rank1_mfma<NT, TPW, 64, 1, true> : (const void *)k_rank1_mfma<NT, TPW, 64, 1, false>;
+}
+const void *isv_solver_kernel(SolverRole r, KernelInst i, bool ex, int nt) {
+    static const void *(*const rank1_for_nt[8])(SolverRole, bool) = {rank1_kernel<1>, rank1_kernel<2>, rank1_kernel<3>, rank1_kernel<4>,
+                                                                     rank1_kernel<5>, rank1_kernel<6>, rank1_kernel<7>, rank1_kernel<8>};
+    if (i == KI_NONE) return nullptr;
+    switch (r) {
+    case KR_SOLVE:
+        if (i == KI_DENSE) return (const void *)k_build_solve;
+        if (i == ST_N11) return (const void *)k_build_solve_st<false, 11>;
+        if (i == ST_RT) return (const void *)k_build_solve_st<false, 0>;
+        if (i == ST_N18) return (const void *)k_build_solve_st<true, 18>;
+        if (i == ST_BIG) return (const void *)k_build_solve_st<true, 0>;
+        return solve_sb_kernel<0>(i);
+    case KR_CHAIN: return solve_sb_kernel<1>(i);
+    case KR_POSE: return solve_sb_kernel<2>(i);
+    case KR_LIN_GRAM_CHAIN:
+        if (ex) return i == LGC_RT ? (const void *)k_lin_gram_chain<true, false, 0, 0> : (const void *)k_lin_gram_chain<true, true, 0, 0>;
+        return i == LGC_N11 ? (const void *)k_lin_gram_chain<false, false, 11, 0> : i == LGC_RT ? (const void *)k_lin_gram_chain<false, false, 0, 0> : (const void *)k_lin_gram_chain<false, true, 0, 0>;
+    case KR_LIN_GRAM_CHAIN_R1: return (const void *)k_lin_gram_chain<false, true, 0, 7>;
+    case KR_POSE_DOGLEG: return ex ? (const void *)k_pose_dogleg<false, 0, true> : i == PD_N11 ? (const void *)k_pose_dogleg<false, 11, false> : (const void *)k_pose_dogleg<false, 0, false>;
+    case KR_RANK1: case KR_RANK1_SPLIT: case KR_SCHUR_SPLIT: return rank1_for_nt[nt - 1](r, ex);     // (lds_T: wd_ld <= 128, so 1 <= nt <= 8)
+    case KR_LIN_GRAM: return ex ? (const void *)k_lin_gram<true, LG_WAVES> : (const void *)k_lin_gram<false, LG_WAVES>;
+    case KR_LIN_GRAM_SMALL: return ex ? (const void *)k_lin_gram<true, LG_WAVES_SMALL> : (const void *)k_lin_gram<false, LG_WAVES_SMALL>;
+    case KR_DOGLEG: return ex ? (const void *)k_dogleg<false, true> : (const void *)k_dogleg<false, false>;
+    case KR_DOGLEG_CONTROL: return ex ? (const void *)k_dogleg<true, true> : (const void *)k_dogleg<true, false>;
+    case KR_STEP_CONTROL: return ex ? (const void *)k_step_control<true, true> : (const void *)k_step_control<true, false>;
+    case KR_SWEEP: return (const void *)k_sweep_mfma;
+    case KR_FRONT: return (const void *)k_front;
+    default: return nullptr;
     }
 }
 
 int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, std::vector<void *> &allocs, std::string &err) {
+    // 1. the environment, 2. the device: compute units, and the workgroups of k_dogleg<true, EX> per CU by registers alone (a small
+    // dynamic LDS request; the LDS bound is applied per upload)
+    hc.env = solve_env_read();
+    int dev0 = 0, per_cu = 0;
+    HCHK(hipGetDevice(&dev0));
+    if (hipDeviceGetAttribute(&hc.dev.n_cus, hipDeviceAttributeMultiprocessorCount, dev0) != hipSuccess) { (void)hipGetLastError(); hc.dev.n_cus = 0; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, isv_solver_kernel(KR_DOGLEG_CONTROL, KI_PLAIN, d.est_ex != 0, 0), 256, 1024) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+    hc.dev.dogleg_per_cu_regs = per_cu;
+    // 3. the sizes that live beside their kernels, 4. the plan
+    SolveShape shape;
+    shape.N = d.N; shape.Nr = d.Nr; shape.est_ex = d.est_ex; shape.n_prior_slots = d.n_prior_slots; shape.prior_H_sz = d.prior_H_sz; shape.max_lm = d.max_lm; shape.max_batch = B;
+    SolveSizes sz;
+    sz.build_solve_sb_bytes = build_solve_sb_bytes(d.N, d.prior_H_sz); sz.build_solve_st_bytes = build_solve_st_bytes(d.N, d.prior_H_sz);
+    sz.build_solve_lds_bytes = build_solve_lds_bytes(d.N); sz.front_lds_bytes = front_lds_bytes(d.N, d.n_prior_slots);
+    sz.build_solve_st_ws_doubles = build_solve_st_ws_doubles(d.N); sz.build_solve_cs_doubles = build_solve_cs_doubles(d.N);
+    hc.plan = plan_handle(shape, hc.env, hc.dev, sz);
+    const HandlePlan &p = hc.plan;
+    if (hc.env.debug_path) {
+        char line[512];
+        plan_format_lds(line, sizeof(line), p); fputs(line, stderr);
+        plan_format_solve_st(line, sizeof(line), p); fputs(line, stderr);
+        plan_format_handle(line, sizeof(line), p, hc.env); fputs(line, stderr);
+    }
+    // 5. what the plan names
+    d.tvis_sz = p.tvis_sz; d.wd_ld = p.wd_ld; d.lds_T = p.lds_T ? 1 : 0; d.r1_dense = p.r1_dense ? 1 : 0; d.split_cap = p.split_cap;
+    d.sw_global = 0; d.marg_scratch_sz = 26;
+    d.sw_part = nullptr; d.st_ws = nullptr; d.cs_ws = nullptr; d.r1_part = nullptr;
     const size_t n = d.np, NI = B * (d.N - 1);
     TRYA(dal(&d.scale_p, B * n, allocs, err)); TRYA(dal(&d.diag_p, B * n, allocs, err)); TRYA(dal(&d.grad_p, B * n, allocs, err));
     TRYA(dal(&d.gn_p, B * n, allocs, err)); TRYA(dal(&d.delta_p, B * n, allocs, err)); TRYA(dal(&d.zp, B * n, allocs, err)); TRYA(dal(&d.up, B * n, allocs, err));
@@ -306,335 +363,159 @@ int isv_solver_alloc(DevBatch &d, SolverHost &hc, size_t B, size_t L, size_t F, 
     TRYA(dal(&d.fcost_c, F, allocs, err)); TRYA(dal(&d.imu_cost_c, NI, allocs, err)); TRYA(dal(&d.prior_cost_c, B * (size_t)d.n_prior_slots, allocs, err)); TRYA(dal(&d.cost_c, B, allocs, err));
     TRYA(dal(&d.fmodel, F, allocs, err)); TRYA(dal(&d.imu_model, NI, allocs, err)); TRYA(dal(&d.prior_model, B * (size_t)d.n_prior_slots, allocs, err)); TRYA(dal(&d.model, B, allocs, err));
     // (the traces, d.marg, d.margin_old, d.header0: transfer buffers, placed by the caller -- isv_batch_buffers.h)
-    d.tvis_sz = 36 * (d.N * (d.N + 1) / 2) + 18 * d.N;
     TRYA(dal(&d.W, (F + L) * 6, allocs, err)); TRYA(dal(&d.lm_cg, L, allocs, err));
-    d.wd_ld = 16 * ((6 * d.N + 16) / 16);          // 6N pose columns + the g_l column, rounded up to 16
     TRYA(dal(&d.Tvis, B * (size_t)d.tvis_sz, allocs, err));
     TRYA(dal(&d.dbg, B * 64, allocs, err)); TRYA(dal(&d.act, ISV_MAX_TRACE, allocs, err));
     HCHK(hipMemset(d.dbg, 0, B * 64 * sizeof(double)));
-    const size_t nblkT = (size_t)d.N * (d.N + 1) / 2 * 225;
-    // LDS-resident fast path: the structure-aware solve (two windows per CU up to N = 11, one beyond), the pair
-    // partials of k_sweep_mfma and the panel + landmark tables of k_rank1_mfma must fit the 160 KB of a CU
-    // (+ the compacted downdates' landmark lists, 64 bytes per output tile: isv_rank1.h -- added below, where they still fit a CU;
-    //  whether the handle takes the LDS path is decided WITHOUT them, as before: the dense loop gives the same bits)
-    size_t lds_r1 = (64 * (size_t)(d.wd_ld + 4) + (size_t)d.max_lm * 3 + 2) * sizeof(double);
-    const size_t n_pairs = (size_t)d.N * (d.N - 1) / 2;
-    const bool sw_global = n_pairs * 84 * sizeof(double) > 40 * 1024;      // partials too big to share a CU's LDS four ways
-    const size_t lds_sw = (n_pairs * 84 + (n_pairs + 2) / 2 + 1) * sizeof(double);       // (the LDS variant's size; the global one needs less)
-    const size_t lds_sb = build_solve_sb_bytes(d.N, d.prior_H_sz);
-    d.lds_T = (d.N <= 20 && d.wd_ld <= 128 && d.prior_H_sz <= 1024 && lds_sb <= (d.N <= 11 ? 80u : 160u) * 1024 &&
-               lds_r1 <= 160 * 1024 && lds_sw <= 160 * 1024) ? 1 : 0;
-    if (getenv("ISV_DEBUG_PATH")) fprintf(stderr, "isv: N=%d wd_ld=%d prior_H_sz=%d lds_sb=%zu lds_r1=%zu lds_sw=%zu -> lds_T=%d\n", d.N, d.wd_ld, d.prior_H_sz, lds_sb, lds_r1, lds_sw, d.lds_T);
-    TRYA(dal(&d.Tglob, d.lds_T ? 1 : B * nblkT, allocs, err));
-    d.sw_part = nullptr; d.sw_global = 0;
-    // ISV_DEBUG_SW_GLOBAL=1 (test hook): give every LDS-path handle the global pair-partial scratch and use it for
-    // every launch, so that small batches exercise the variant large N >= 12 batches run
-    hc.one_stream = getenv("ISV_ONE_STREAM") != nullptr; hc.split_control = getenv("ISV_SPLIT_CONTROL") != nullptr;
-    hc.generic_n = getenv("ISV_GENERIC_N") != nullptr; hc.lg_batch_waves = getenv("ISV_LG_BATCH_WAVES") != nullptr;
-    hc.debug_sw_global = getenv("ISV_DEBUG_SW_GLOBAL") != nullptr; hc.legacy_visual = getenv("ISV_LEGACY_VISUAL") != nullptr;
-    hc.no_split = getenv("ISV_NO_SPLIT") != nullptr;
-    hc.no_update = getenv("ISV_DEBUG_NO_UPDATE") != nullptr; hc.no_pose_dogleg = getenv("ISV_NO_POSE_DOGLEG") != nullptr;
-    hc.marg_one_kernel = getenv("ISV_MARG_ONE_KERNEL") != nullptr; hc.marg_split = getenv("ISV_MARG_SPLIT") != nullptr;
-    hc.tail_one_wave = getenv("ISV_TAIL_ONE_WAVE") != nullptr;
-    // the rank-1 downdates' per-tile landmark lists, unless ISV_R1_DENSE asks for the dense loop or the lists do not fit the CU's LDS
-    // beside the panel and the landmark tables (max_landmarks near 4000 at 20 frames): the dense loop then, on the same LDS as before
-    hc.r1_dense = getenv("ISV_R1_DENSE") != nullptr || lds_r1 + rank1_list_bytes(d.wd_ld / 16) > ISV_LDS_PER_CU;
-    d.r1_dense = hc.r1_dense ? 1 : 0;
-    if (!hc.r1_dense) lds_r1 += rank1_list_bytes(d.wd_ld / 16);
-    int dev0_ = 0;
-    HCHK(hipGetDevice(&dev0_));
-    if (hipDeviceGetAttribute(&hc.n_cus, hipDeviceAttributeMultiprocessorCount, dev0_) != hipSuccess) { (void)hipGetLastError(); hc.n_cus = 0; }
-    // one long window over many CUs (k_schur_split): possible on this handle when a window can have ISV_SPLIT_MIN_PASSES passes
-    const bool can_split = d.lds_T && !d.est_ex && !hc.no_split && ((size_t)d.max_lm + 63) / 64 >= ISV_SPLIT_MIN_PASSES && hc.n_cus > ISV_SPLIT_MIN_PASSES;
-    if (d.lds_T && (sw_global || hc.debug_sw_global || can_split)) TRYA(dal(&d.sw_part, B * n_pairs * 84, allocs, err));
-    hc.sw_global_ok = sw_global || hc.debug_sw_global;
-    hc.cap_batch = B;
-    // k_build_solve_st (isv_build_solve_st.hip): a quarter (N <= 11) / half of a CU's LDS per window, 256 threads.  It wins when
-    // the batch fills the GPU more than twice over with k_build_solve_sb's two (one) windows per CU; a window alone on a CU is
-    // faster with the 512-thread kernel.  The choice is per HANDLE (its max_batch): a window gives the same bits alone and in any
-    // batch of the same handle.
-    d.st_ws = nullptr;
-    {
-        const size_t lds_st = build_solve_st_bytes(d.N, d.prior_H_sz);
-        const bool fits = d.lds_T && (d.N <= 11 ? lds_st <= 40 * 1024 : lds_st <= 80 * 1024);
-        const char *e = getenv("ISV_SOLVE_ST");
-        const size_t per_cu_sb = d.N <= 11 ? 2 : 1;
-        // (measured: N = 11, 1024 windows: 180 -> 146 us per launch, 182 -> 190-193 k windows/s, 512 windows: 3.55 against 3.22 ms;
-        //  N = 18 (512 threads, two windows per CU), 1024 windows: 11.09 -> 10.33 ms per step, 512: 5.99 -> 5.61, 256: 3.27 -> 3.68:
-        //  only handles whose batches exceed the resident windows of k_build_solve_sb take it)
-        hc.solve_st = fits && (e ? atoi(e) != 0 : B > per_cu_sb * (size_t)hc.n_cus);
-        if (getenv("ISV_DEBUG_PATH")) fprintf(stderr, "isv: k_build_solve_st lds=%zu fits=%d -> solve_st=%d\n", lds_st, (int)fits, (int)hc.solve_st);
-        if (hc.solve_st) TRYA(dal(&d.st_ws, B * build_solve_st_ws_doubles(d.N), allocs, err));
+    TRYA(dal(&d.Tglob, p.lds_T ? 1 : B * ((size_t)d.N * (d.N + 1) / 2 * 225), allocs, err));
+    if (p.has_sw_part) TRYA(dal(&d.sw_part, B * p.n_pairs * 84, allocs, err));
+    if (p.solve_st) TRYA(dal(&d.st_ws, B * sz.build_solve_st_ws_doubles, allocs, err));
+    if (p.chain_split) {       // (entries above the diagonal of a diagonal block are never written: finite)
+        TRYA(dal(&d.cs_ws, B * sz.build_solve_cs_doubles, allocs, err));
+        HCHK(hipMemset(d.cs_ws, 0, B * sz.build_solve_cs_doubles * sizeof(double)));
     }
-    // the split solve (isv_build_solve_sb.hip, MODE 1 / 2): handles that run k_build_solve_sb and whose batches leave CUs idle -- the chain
-    // kernel needs a CU of its own beside k_lin_gram / k_rank1_mfma to take the speed/bias elimination off the critical path
-    d.cs_ws = nullptr;
-    {
-        const char *e = getenv("ISV_CHAIN_SPLIT");
-        hc.chain_split = d.lds_T && !hc.solve_st && (e ? atoi(e) != 0 : B <= (size_t)hc.n_cus);
-        if (hc.chain_split) { TRYA(dal(&d.cs_ws, B * build_solve_cs_doubles(d.N), allocs, err)); HCHK(hipMemset(d.cs_ws, 0, B * build_solve_cs_doubles(d.N) * sizeof(double))); }     // (entries above the diagonal of a diagonal block are never written: finite)
-    }
-    d.r1_part = nullptr;
-    // groups per window (DevBatch::split_cap), PER HANDLE (its max_batch and max_landmarks): a window is split the same way alone and inside
-    // any batch of the handle.  All or nothing: the split pays while every group of every window of a full batch finds a CU of its own
-    // (measured, round 5: with two groups' workgroups per CU -- 128 windows x 4 groups, 256 x 2 -- the partial tiles' traffic, 123 KB per
-    // window and group against 20 KB of Tvis, and the fold launch cost what the shorter passes save: 1.89 -> 1.90 ms, 2.35 -> 2.45 ms).
-    d.split_cap = 1;
-    if (can_split) {
-        const size_t pm = ((size_t)d.max_lm + 63) / 64, gmH = pm < ISV_SPLIT_MAX_GROUPS ? pm : ISV_SPLIT_MAX_GROUPS;
-        if (B * (gmH + 1) <= (size_t)hc.n_cus) d.split_cap = ISV_SPLIT_MAX_GROUPS;
-    }
-    if (can_split && d.split_cap >= 2) {
-        const size_t nt_ = d.wd_ld / 16, pm = ((size_t)d.max_lm + 63) / 64, gm = pm < (size_t)d.split_cap ? pm : (size_t)d.split_cap;
-        TRYA(dal(&d.r1_part, B * gm * (nt_ * (nt_ + 1) / 2) * 256, allocs, err));
-    }
-    d.marg_scratch_sz = 26;
+    if (p.r1_groups) TRYA(dal(&d.r1_part, B * p.r1_groups * (size_t)(p.nt * (p.nt + 1) / 2) * 256, allocs, err));
     TRYA(dal(&d.marg_scratch, L * 26, allocs, err));
     TRYA(dal(&d.marg_ws, B * ISV_MARG_WS, allocs, err));
-    // the kernel table: the instantiation of every role this handle can launch
-    SolverKernel *k = hc.kern;
-    const bool ex = d.est_ex != 0, gn = hc.generic_n;
-    const int N = d.N;
-    k[KR_DOGLEG] = {ex ? (const void *)k_dogleg<false, true> : (const void *)k_dogleg<false, false>, 256, 0};
-    k[KR_DOGLEG_CONTROL] = {ex ? (const void *)k_dogleg<true, true> : (const void *)k_dogleg<true, false>, 256, 0};
-    k[KR_STEP_CONTROL] = {ex ? (const void *)k_step_control<true, true> : (const void *)k_step_control<true, false>, 256, 0};
-    if (!d.lds_T) k[KR_SOLVE] = {(const void *)k_build_solve, 512, build_solve_lds_bytes(N)};
-    else {
-        k[KR_SWEEP] = {(const void *)k_sweep_mfma, 64 * ISV_SWEEP_WAVES, lds_sw};
-        // lds_T: wd_ld <= 128, so 1 <= nt <= 8
-        static void (*const rank1_for_nt[8])(SolverKernel *, bool, bool, size_t, size_t) = {
-            set_rank1_kernels<1>, set_rank1_kernels<2>, set_rank1_kernels<3>, set_rank1_kernels<4>,
-            set_rank1_kernels<5>, set_rank1_kernels<6>, set_rank1_kernels<7>, set_rank1_kernels<8>};
-        const size_t lds_sp = lds_r1 > (2 * n_pairs + 2) * sizeof(int) ? lds_r1 : (2 * n_pairs + 2) * sizeof(int);
-        rank1_for_nt[d.wd_ld / 16 - 1](k, ex, d.r1_part != nullptr, lds_r1, lds_sp);
-        // k_lin_gram: up to the whole CU (the launch sizes its LDS from the uploaded windows: isv_batch_upload)
-        auto lg_cap = [&](int waves) { const size_t b = lin_gram_lds_bytes(d.Nr, true, ex, waves, d.max_lm); return b < ISV_LDS_PER_CU ? b : ISV_LDS_PER_CU; };
-        k[KR_LIN_GRAM] = {ex ? (const void *)k_lin_gram<true, LG_WAVES> : (const void *)k_lin_gram<false, LG_WAVES>, 64 * LG_WAVES, lg_cap(LG_WAVES)};
-        k[KR_LIN_GRAM_SMALL] = {ex ? (const void *)k_lin_gram<true, LG_WAVES_SMALL> : (const void *)k_lin_gram<false, LG_WAVES_SMALL>, 64 * LG_WAVES_SMALL, lg_cap(LG_WAVES_SMALL)};
-        if (hc.solve_st) {
-            // (the reference's ALL_BUF_SIZE as a compile-time constant: 404 -> 357 us per launch, 1024 windows 10.27 -> 9.87 ms.  The same for
-            //  k_build_solve_sb<true, 18> spills 62 registers and is SLOWER for the single window it serves: 2.54 against 2.48 ms; not instantiated)
-            const void *fn = N == 11 && !gn ? (const void *)k_build_solve_st<false, 11> : N <= 11 ? (const void *)k_build_solve_st<false, 0>
-                           : N == 18 && !gn ? (const void *)k_build_solve_st<true, 18> : (const void *)k_build_solve_st<true, 0>;
-            k[KR_SOLVE] = {fn, N <= 11 ? 256u : 512u, build_solve_st_bytes(N, d.prior_H_sz)};      // (long windows: eight wavefronts, two windows per CU)
-        } else if (!hc.chain_split) k[KR_SOLVE] = {solve_sb_kernel<0>(N, gn), 512, lds_sb};
-        else {
-            k[KR_CHAIN] = {solve_sb_kernel<1>(N, gn), 512, lds_sb};
-            k[KR_POSE] = {solve_sb_kernel<2>(N, gn), 512, lds_sb};
-            k[KR_FRONT] = {(const void *)k_front, 512, front_lds_bytes(N, d.n_prior_slots)};
-            // k_lin_gram_chain: the larger of its two roles' needs
-            size_t lgc = lin_gram_lds_bytes(d.Nr, true, ex, LG_WAVES_SMALL, d.max_lm);
-            if (lgc < lds_sb) lgc = lds_sb;
-            if (lgc < lds_r1) lgc = lds_r1;
-            if (lgc > ISV_LDS_PER_CU) lgc = ISV_LDS_PER_CU;
-            const void *fn = ex ? (N <= 11 ? (const void *)k_lin_gram_chain<true, false, 0, 0> : (const void *)k_lin_gram_chain<true, true, 0, 0>)
-                           : N == 11 && !gn ? (const void *)k_lin_gram_chain<false, false, 11, 0>
-                           : N <= 11 ? (const void *)k_lin_gram_chain<false, false, 0, 0> : (const void *)k_lin_gram_chain<false, true, 0, 0>;
-            k[KR_LIN_GRAM_CHAIN] = {fn, 512, lgc};
-            // the rank-1 downdates in the same workgroup (the shapes instantiated for it)
-            if (!ex && !gn && N > 11 && d.wd_ld / 16 == 7 && lds_r1 <= ISV_LDS_PER_CU) k[KR_LIN_GRAM_CHAIN_R1] = {(const void *)k_lin_gram_chain<false, true, 0, 7>, 512, lgc};
-            // k_pose_dogleg: the pose half's LDS or the dogleg / step control's, whichever is larger (the latter is sized per enqueue: up to a CU).
-            // 11 frames and fewer only (measured: 128 windows of 11 frames 1.92 -> 1.86 ms; the 18-frame form LOSES -- 117 us against 70 + 37
-            // for the two launches, rocprofv3)
-            if (N <= 11 && !hc.no_pose_dogleg) {
-                const void *pd = ex ? (const void *)k_pose_dogleg<false, 0, true> : N == 11 && !gn ? (const void *)k_pose_dogleg<false, 11, false> : (const void *)k_pose_dogleg<false, 0, false>;
-                k[KR_POSE_DOGLEG] = {pd, 512, ISV_LDS_PER_CU - 4096};
-            }
-        }
-    }
-    hc.debug_path = getenv("ISV_DEBUG_PATH") != nullptr;
-    if (hc.debug_path)
-        fprintf(stderr, "isv: handle chain_split=%d generic_n=%d no_pose_dogleg=%d lg_batch_waves=%d split_control=%d legacy_visual=%d pose_dogleg_kernel=%d r1_in_lg_kernel=%d split_cap=%d\n",
-                (int)hc.chain_split, (int)hc.generic_n, (int)hc.no_pose_dogleg, (int)hc.lg_batch_waves, (int)hc.split_control, (int)hc.legacy_visual,
-                k[KR_POSE_DOGLEG].fn ? 1 : 0, k[KR_LIN_GRAM_CHAIN_R1].fn ? 1 : 0, (int)d.split_cap);
-    for (const SolverKernel &e : hc.kern) HCHK(isv_raise_dynamic_lds(e.fn, dev0_, e.lds));
-    // device figures the per-launch variant choice needs (once per handle, not per isv_batch_optimize): hc.n_cus (above) and the
-    // workgroups of k_dogleg<true, EX> per CU by registers alone (a small dynamic LDS request); the LDS bound is applied per enqueue
-    {
-        int per_cu = 0;
-        if (d.lds_T && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k[KR_DOGLEG_CONTROL].fn, 256, 1024) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-        hc.dogleg_per_cu_regs = per_cu;
+    // 6. the kernel table, 7. the dynamic-LDS attributes
+    for (int r = 0; r < KR_COUNT; r++) {
+        hc.fn[r] = isv_solver_kernel((SolverRole)r, p.roles[r].inst, d.est_ex != 0, p.nt);
+        HCHK(isv_raise_dynamic_lds(hc.fn[r], dev0, p.roles[r].lds));
     }
     return ISV_OK;
 }
 
-// launch table entry k with the arguments a: the runtime receives the same kernel handle as from hipLaunchKernelGGL of the
-// instantiation, and a failed launch surfaces at the enqueue's closing hipGetLastError like theirs
-template <typename... A> static void launch(const SolverKernel &k, dim3 grid, size_t lds, hipStream_t s, A... a) {
-    void *args[] = {&a...};
-    (void)hipLaunchKernel(k.fn, grid, dim3(k.threads), args, lds, s);
+UploadPlan isv_solver_plan_upload(SolverHost &hc, const UploadShape &u) {
+    hc.upload = u;
+    return plan_upload(hc.plan, hc.dev, hc.env, u);
 }
 
+// launch role r with the arguments a: the runtime receives the same kernel handle as from hipLaunchKernelGGL of the
+// instantiation, and a failed launch surfaces at the enqueue's closing hipGetLastError like theirs
+template <typename... A> static void launch(const SolverHost &hc, SolverRole r, dim3 grid, size_t lds, hipStream_t s, A... a) {
+    void *args[] = {&a...};
+    (void)hipLaunchKernel(hc.fn[r], grid, dim3(hc.plan.roles[r].threads), args, lds, s);
+}
+
+// Enqueues the resident upload's solve by its plan (plan_upload, isv_solve_plan.h: every choice, grid and LDS size below is a field of it).
 // prof_ev (optional): [max_iter][ISV_PROF_FAMILIES][2] events recorded around the three dominant
 // kernel families on the solve stream, so bench.py can report per-kernel durations measured live.
 int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStream_t st2, hipEvent_t *fj, int64_t *counts, hipEvent_t *prof_ev, std::string &err) {
     // st2 / fj[4]: side stream + fork/join events: the IMU and prior factor kernels are latency-bound and
     // independent of the reprojection pipeline, so they run beside it and are joined before their consumers
 #define PROF(slot, fam, which) do { if (prof_ev) (void)hipEventRecord(prof_ev[((slot) * ISV_PROF_FAMILIES + (fam)) * 2 + (which)], st); } while (0)
-    const SolverKernel *K = hc.kern;
-    const size_t NI = (size_t)d.B * (d.N - 1);
-    const size_t lds_proj = 4 * proj_lds_doubles_per_wave(d.N, 0) * sizeof(double), lds_proj1 = 4 * proj_lds_doubles_per_wave(d.N, 1) * sizeof(double);
-    if (hc.one_stream) st2 = st;            // diagnostics: serialise everything on one stream (per-kernel timelines)
-    d.ctl_stage_lm = (6 * (size_t)d.lg_lcap * sizeof(double) <= ISV_CTL_STAGE_MAX_BYTES) ? 1 : 0;
-    // the priors' J^T J record is staged in k_dogleg's LDS while that keeps the batch in one resident round (else: read from global)
-    d.dg_stage_ph = 1;
-    if (ISV_LDS_PER_CU / ((dogleg_lds_bytes(d) > step_control_lds_bytes(d) ? dogleg_lds_bytes(d) : step_control_lds_bytes(d)) + 2304) * (size_t)hc.n_cus < (size_t)d.B) d.dg_stage_ph = 0;
-    const size_t lds_dg = dogleg_lds_bytes(d), lds_sc = step_control_lds_bytes(d);
-    const size_t lds_dgc = lds_dg > lds_sc ? lds_dg : lds_sc;
-    // workgroups of k_dogleg<true> a CU holds: registers (hc) and LDS (dynamic + the 2 KB of static reduction space)
-    const size_t dg_by_lds = ISV_LDS_PER_CU / (lds_dgc + 2304);
-    const size_t res_dogleg_ctl = (size_t)hc.n_cus * ((size_t)hc.dogleg_per_cu_regs < dg_by_lds ? (size_t)hc.dogleg_per_cu_regs : dg_by_lds);
-    // dogleg + step control in one kernel while the batch fits ONE resident round of it (it holds fewer workgroups per CU
-    // than k_dogleg<false>: at 2048 windows the fused kernel needs a second round and the step is 21 % slower, measured);
-    // same arithmetic either way (bitwise, tests/test_gpu_branches.py)
-    // (a free extrinsic is only evaluated by the per-window kernels: k_proj_linearize<1> reads the constant one)
-    const bool control_in_wg = d.lds_T && ((size_t)d.Ftot <= (size_t)4096 * d.B || d.est_ex);
-    const bool fuse_control = control_in_wg && !hc.split_control && (size_t)d.B <= res_dogleg_ctl;
-    const int n_cus = hc.n_cus;
-    // Small-batch handles (hc.chain_split: every workgroup of every kernel finds a CU of its own) run the whole iteration on ONE
-    // stream: an event record costs the critical stream ~7 us and a wait that really blocks ~13 us on this GPU (measured, rocprofv3
-    // kernel trace of one window), more than the kernels they would overlap.  Instead, independent work shares a LAUNCH:
-    // k_front = {IMU factors | prior factors} of every window, k_lin_gram_chain = {k_lin_gram | chain half of the split solve}.
-    const bool cs = hc.chain_split;
-    // (what the visual part of this upload will run, needed here already: k_lin_gram_chain or not)
-    const bool fused = d.lds_T && d.fused_visual;
-    d.sw_global = (d.sw_part && hc.sw_global_ok && (d.B > 256 || hc.debug_sw_global)) ? 1 : 0;     // more than one workgroup per CU: trade LDS for occupancy
-    const int lgw = (fused && d.B <= n_cus && !hc.lg_batch_waves && lin_gram_lds_bytes(d.Nr, !d.sw_global, d.est_ex != 0, LG_WAVES_SMALL, d.lg_lcap) <= ISV_LDS_PER_CU) ? LG_WAVES_SMALL : LG_WAVES;
-    // k_lin_gram_chain takes the chain half; an upload it does not take (windows beyond the fused kernel's limits: BASELINE config 5's
-    // 30 000 factors) runs the chain half (~75 us at 20 frames) on the side stream beside the linearisation and the split elimination --
-    // worth its fork / join events there (on the solve stream behind them it made the one-launch solve's 142 us into 75 + 75)
-    const bool lg_chain = cs && fused && lgw == LG_WAVES_SMALL;
-    // a SMALL batch with LONG windows: one window's elimination over many CUs (k_schur_split + k_schur_fold, isv_sweep.hip)
-    // WHETHER a window's downdates are split is decided by the HANDLE (its max_batch and max_landmarks: ADVICE r4 -- with the groups
-    // counted from the longest window of the upload, a 320-landmark window was split alone and unsplit beside a 2048-landmark one);
-    // into how many groups, by the window (schur_split_groups).  An upload without a window of ISV_SPLIT_MIN_PASSES passes skips
-    // the split launch: its windows are one group each, the unsplit sums.
-    const int Pmax = (d.lg_lcap + 63) / 64, PmaxH = (d.max_lm + 63) / 64, GrMax = PmaxH < d.split_cap ? PmaxH : d.split_cap;
-    const bool split = d.lds_T && d.r1_part && !hc.no_split && Pmax >= ISV_SPLIT_MIN_PASSES && d.split_cap >= 2;
-    // the rank-1 downdates inside k_lin_gram_chain (handles that do not split the elimination)
-    const bool r1_in_lg = lg_chain && K[KR_LIN_GRAM_CHAIN_R1].fn && !split;
-    // the landmark back-substitution on its own workgroups (k_backsub_split) pays for LONG windows only: per landmark it is the same
-    // routine as k_dogleg's first phase (same bits), which takes ~2.5 us for 300 landmarks against 6-8 us for the extra launch
-    const bool bsub_split = split && d.lg_lcap > 1024;
-    d.bs_split = bsub_split ? 1 : 0;
-    // the pose half of the split solve + k_dogleg<true> (dogleg and step control) in one launch: same routines, same bits
-    // (+ the 2 KB of static reduction space)
-    const size_t lds_pd = K[KR_POSE].lds > lds_dgc ? K[KR_POSE].lds : lds_dgc;
-    const bool pose_dogleg = K[KR_POSE_DOGLEG].fn && fuse_control && !bsub_split && lds_pd + 2304 <= ISV_LDS_PER_CU;
-    if (hc.debug_path)
-        fprintf(stderr, "isv: enqueue B=%d lg_lcap=%d fused=%d lgw=%d lg_chain=%d r1_in_lg=%d split=%d bsub_split=%d fuse_control=%d pose_dogleg=%d\n",
-                d.B, d.lg_lcap, (int)fused, lgw, (int)lg_chain, (int)r1_in_lg, (int)split, (int)bsub_split, (int)fuse_control, (int)pose_dogleg);
-    hipLaunchKernelGGL(k_init_state, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
+    UploadShape shape = hc.upload;
+    shape.init_mode = d.init_mode;
+    const UploadPlan p = plan_upload(hc.plan, hc.dev, hc.env, shape);
+    const RolePlan *K = hc.plan.roles;
+    const unsigned B = (unsigned)p.B;
+    d.ctl_stage_lm = p.ctl_stage_lm ? 1 : 0; d.dg_stage_ph = p.dg_stage_ph ? 1 : 0; d.sw_global = p.sw_global ? 1 : 0; d.bs_split = p.bsub_split ? 1 : 0;
+    if (hc.env.debug_path) { char line[512]; plan_format_enqueue(line, sizeof(line), p); fputs(line, stderr); }
+    if (hc.env.one_stream) st2 = st;            // diagnostics: serialise everything on one stream (per-kernel timelines)
+    hipLaunchKernelGGL(k_init_state, dim3(p.grid_init_state), dim3(64), 0, st, d);
     for (int slot = 0; slot < d.max_iter; slot++) {
         // linearise where needed (k_*_linearize skip windows whose need_linearize == 0 via the tile/window flags)
-        if (cs) {
-            launch(K[KR_FRONT], dim3(d.B, 2), K[KR_FRONT].lds, st, d);
-            if (!lg_chain) {
+        // Small-batch handles (chain_split: every workgroup of every kernel finds a CU of its own) run the whole iteration on ONE
+        // stream: an event record costs the critical stream ~7 us and a wait that really blocks ~13 us on this GPU (measured, rocprofv3
+        // kernel trace of one window), more than the kernels they would overlap.  Instead, independent work shares a LAUNCH:
+        // k_front = {IMU factors | prior factors} of every window, k_lin_gram_chain = {k_lin_gram | chain half of the split solve}.
+        // An upload k_lin_gram_chain does not take (windows beyond the fused kernel's limits: BASELINE config 5's 30 000 factors) runs
+        // the chain half (~75 us at 20 frames) on the side stream beside the linearisation and the split elimination -- worth its fork /
+        // join events there (on the solve stream behind them it made the one-launch solve's 142 us into 75 + 75)
+        if (p.chain_split) {
+            launch(hc, KR_FRONT, dim3(B, 2), K[KR_FRONT].lds, st, d);
+            if (!p.lg_chain) {
                 HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
-                launch(K[KR_CHAIN], dim3(d.B), K[KR_CHAIN].lds, st2, d);
+                launch(hc, KR_CHAIN, dim3(B), K[KR_CHAIN].lds, st2, d);
                 HCHK(hipEventRecord(fj[1], st2));
             }
         } else {
             HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
-            if (NI) {
-                hipLaunchKernelGGL(k_imu_raw, dim3((unsigned)(NI + 63) / 64), dim3(256), 0, st2, d, d.pose, d.sb, 1);
-                hipLaunchKernelGGL(k_imu_weight, dim3((unsigned)(NI + 7) / 8), dim3(256), 0, st2, d, d.imu_cost, 1);
+            if (p.has_imu) {
+                hipLaunchKernelGGL(k_imu_raw, dim3(p.grid_imu_raw), dim3(256), 0, st2, d, d.pose, d.sb, 1);
+                hipLaunchKernelGGL(k_imu_weight, dim3(p.grid_imu_weight), dim3(256), 0, st2, d, d.imu_cost, 1);
             }
-            hipLaunchKernelGGL(k_prior_linearize<true>, dim3(d.B), dim3(64), prior_lds_bytes(d.n_prior_slots), st2, d, d.pose, d.sb, d.prior_cost, 1);
+            hipLaunchKernelGGL(k_prior_linearize<true>, dim3(B), dim3(64), p.lds_prior, st2, d, d.pose, d.sb, d.prior_cost, 1);
             HCHK(hipEventRecord(fj[1], st2));
         }
         PROF(slot, 0, 0);
-        if (fused) {
+        if (p.fused) {
             // linearisation fused with the Gram products: no Jacobian strip goes to HBM (isv_visual.hip)
             // (eight wavefronts per window while the batch leaves every window a CU of its own: 41 -> 27 us per launch for one window)
-            const size_t lds_lg = lin_gram_lds_bytes(d.Nr, !d.sw_global, d.est_ex != 0, lgw, d.lg_lcap);
-            if (lg_chain) {
-                size_t both = lds_lg > K[KR_CHAIN].lds ? lds_lg : K[KR_CHAIN].lds;
-                if (r1_in_lg && both < K[KR_RANK1].lds) both = K[KR_RANK1].lds;
-                launch(K[r1_in_lg ? KR_LIN_GRAM_CHAIN_R1 : KR_LIN_GRAM_CHAIN], dim3(d.B, 2), both, st, d);
-            } else launch(K[lgw == LG_WAVES_SMALL ? KR_LIN_GRAM_SMALL : KR_LIN_GRAM], dim3(d.B), lds_lg, st, d);
+            launch(hc, p.visual_role, dim3(B, p.lg_chain ? 2 : 1), p.lds_visual, st, d);
             counts[ISV_CNT_LINEARIZE]++; counts[ISV_CNT_FUSED_VISUAL] = 1;
-        } else if (d.n_tiles > 0) { hipLaunchKernelGGL(k_proj_linearize<0>, dim3((d.n_tiles + 3) / 4), dim3(256), lds_proj, st, d, d.pose, d.lam, d.fcost, 1); counts[ISV_CNT_LINEARIZE]++; }
+        } else if (p.has_tiles) { hipLaunchKernelGGL(k_proj_linearize<0>, dim3(p.grid_tiles), dim3(256), p.lds_proj, st, d, d.pose, d.lam, d.fcost, 1); counts[ISV_CNT_LINEARIZE]++; }
         PROF(slot, 0, 1);
-        if (split) {
-            int Gs = 0;
-            if (!fused) { Gs = n_cus / d.B - GrMax; if (Gs > 16) Gs = 16; if (Gs < 1) Gs = 1; }
-            const dim3 grid(d.B, Gs + GrMax);
+        if (p.split) {
+            // a SMALL batch with LONG windows: one window's elimination over many CUs (k_schur_split + k_schur_fold, isv_sweep.hip)
+            const dim3 grid(B, p.grid_split_y);
             PROF(slot, 1, 0);
-            if (Gs == 0) launch(K[KR_RANK1_SPLIT], grid, K[KR_RANK1_SPLIT].lds, st, d, GrMax);          // the downdates alone: the lean kernel (two workgroups per CU)
-            else launch(K[KR_SCHUR_SPLIT], grid, K[KR_SCHUR_SPLIT].lds, st, d, Gs, GrMax);
+            if (p.fused) launch(hc, KR_RANK1_SPLIT, grid, K[KR_RANK1_SPLIT].lds, st, d, p.GrMax);          // the downdates alone: the lean kernel (two workgroups per CU)
+            else launch(hc, KR_SCHUR_SPLIT, grid, K[KR_SCHUR_SPLIT].lds, st, d, p.Gs, p.GrMax);
             PROF(slot, 1, 1);
             PROF(slot, 2, 0);
-            const int nt = d.wd_ld / 16;
-            hipLaunchKernelGGL(k_schur_fold, dim3(d.B, nt * (nt + 1) / 2), dim3(256), 0, st, d, GrMax, nt, Gs > 0 ? 1 : 0);      // one accumulator-tile entry per thread
+            hipLaunchKernelGGL(k_schur_fold, dim3(B, p.grid_fold_y), dim3(256), 0, st, d, p.GrMax, hc.plan.nt, p.fused ? 0 : 1);
             PROF(slot, 2, 1);
-            counts[ISV_CNT_ELIM]++; counts[ISV_CNT_SPLIT_GROUPS] = GrMax;
-        } else if (d.lds_T) {
+            counts[ISV_CNT_ELIM]++; counts[ISV_CNT_SPLIT_GROUPS] = p.GrMax;
+        } else if (p.lds_T) {
             // landmark elimination: Gram products of the pose Jacobians, then the rank-1 downdates (both FP64 MFMA)
             PROF(slot, 1, 0);
-            if (!fused) {
-                const size_t n_pairs = (size_t)d.N * (d.N - 1) / 2;
-                launch(K[KR_SWEEP], dim3(d.B), ((d.sw_global ? 0 : n_pairs * 84) + (n_pairs + 2) / 2 + 1) * sizeof(double), st, d);
-            }
+            if (!p.fused) launch(hc, KR_SWEEP, dim3(B), p.lds_sweep, st, d);
             counts[ISV_CNT_ELIM]++;
             PROF(slot, 1, 1);
             // one workgroup per window: nt(nt+1)/2 tile wavefronts, w vectors expanded to panel rows in LDS
             PROF(slot, 2, 0);
-            if (!r1_in_lg) launch(K[KR_RANK1], dim3(d.B), K[KR_RANK1].lds, st, d);
+            if (!p.r1_in_lg) launch(hc, KR_RANK1, dim3(B), K[KR_RANK1].lds, st, d);
             PROF(slot, 2, 1);
         }
-        if (!lg_chain) HCHK(hipStreamWaitEvent(st, fj[1], 0));
-        if (!d.lds_T) hipLaunchKernelGGL(k_cost_reduce, dim3(d.B), dim3(256), 0, st, d, d.fcost, d.imu_cost, d.prior_cost, d.cost, 1);   // (k_build_solve_sb sums the cost itself)
+        if (!p.lg_chain) HCHK(hipStreamWaitEvent(st, fj[1], 0));
+        if (!p.lds_T) hipLaunchKernelGGL(k_cost_reduce, dim3(B), dim3(256), 0, st, d, d.fcost, d.imu_cost, d.prior_cost, d.cost, 1);   // (k_build_solve_sb sums the cost itself)
         PROF(slot, 3, 0);
         // the whole reduced solve, or on chain-split handles its pose half (the chain half ran beside k_lin_gram), with the dogleg
         // and the step control when they fit one launch
-        if (pose_dogleg) { launch(K[KR_POSE_DOGLEG], dim3(d.B), lds_pd, st, d); counts[ISV_CNT_FUSED_CONTROL] = 1; }
-        else if (cs) launch(K[KR_POSE], dim3(d.B), K[KR_POSE].lds, st, d);
-        else launch(K[KR_SOLVE], dim3(d.B), K[KR_SOLVE].lds, st, d);
-        if (hc.solve_st) counts[ISV_CNT_SOLVE_ST] = 1;
+        launch(hc, p.solve_role, dim3(B), p.lds_solve, st, d);
+        if (p.pose_dogleg) counts[ISV_CNT_FUSED_CONTROL] = 1;
+        if (p.solve_st) counts[ISV_CNT_SOLVE_ST] = 1;
         counts[ISV_CNT_SOLVE]++;
         PROF(slot, 3, 1);
         PROF(slot, 4, 0);
-        if (bsub_split) hipLaunchKernelGGL(k_backsub_split, dim3(d.B, (d.lg_lcap + 127) / 128), dim3(128), 2 * (size_t)d.np * sizeof(double), st, d);
-        if (pose_dogleg) {
-        } else if (fuse_control) {
-            launch(K[KR_DOGLEG_CONTROL], dim3(d.B), lds_dgc, st, d);
+        if (p.bsub_split) hipLaunchKernelGGL(k_backsub_split, dim3(B, p.grid_backsub_y), dim3(128), p.lds_backsub, st, d);
+        if (p.pose_dogleg) {
+        } else if (p.fuse_control) {
+            launch(hc, KR_DOGLEG_CONTROL, dim3(B), p.lds_dogleg, st, d);
             counts[ISV_CNT_FUSED_CONTROL] = 1;
-        } else launch(K[KR_DOGLEG], dim3(d.B), lds_dg, st, d);
+        } else launch(hc, KR_DOGLEG, dim3(B), p.lds_dogleg, st, d);
         PROF(slot, 4, 1);
-        if (!d.lds_T) {                    // (the LDS path evaluates these inside k_dogleg)
+        if (!p.lds_T) {                    // (the LDS path evaluates these inside k_dogleg)
             HCHK(hipEventRecord(fj[2], st)); HCHK(hipStreamWaitEvent(st2, fj[2], 0));
-            if (NI) hipLaunchKernelGGL(k_imu_linearize<false>, dim3((unsigned)NI), dim3(64), 0, st2, d, d.cpose, d.csb, d.imu_cost_c, 2);
-            hipLaunchKernelGGL(k_prior_linearize<false>, dim3(d.B), dim3(64), prior_lds_bytes(d.n_prior_slots, false), st2, d, d.cpose, d.csb, d.prior_cost_c, 2);
-            hipLaunchKernelGGL(k_model_imu_prior, dim3(d.B * d.N), dim3(64), 0, st2, d);
+            if (p.has_imu) hipLaunchKernelGGL(k_imu_linearize<false>, dim3(p.grid_imu_c), dim3(64), 0, st2, d, d.cpose, d.csb, d.imu_cost_c, 2);
+            hipLaunchKernelGGL(k_prior_linearize<false>, dim3(B), dim3(64), p.lds_prior_c, st2, d, d.cpose, d.csb, d.prior_cost_c, 2);
+            hipLaunchKernelGGL(k_model_imu_prior, dim3(p.grid_model), dim3(64), 0, st2, d);
             HCHK(hipEventRecord(fj[3], st2));
         }
         // candidate evaluation of the reprojection factors: inside the per-window control kernel, unless the windows are
         // so large that one workgroup per window would serialise it (config 5: 30 000 factors in one window)
         PROF(slot, 5, 0);
-        if (fuse_control) {
-        } else if (control_in_wg) launch(K[KR_STEP_CONTROL], dim3(d.B), lds_sc, st, d);
+        if (p.fuse_control) {
+        } else if (p.control_in_wg) launch(hc, KR_STEP_CONTROL, dim3(B), p.lds_step_control, st, d);
         else {
-            if (d.n_tiles > 0) hipLaunchKernelGGL(k_proj_linearize<1>, dim3((d.n_tiles + 3) / 4), dim3(256), lds_proj1, st, d, d.cpose, d.clam, d.fcost_c, 2);
-            if (!d.lds_T) HCHK(hipStreamWaitEvent(st, fj[3], 0));
-            hipLaunchKernelGGL((k_step_control<false, false>), dim3(d.B), dim3(256), 0, st, d);
+            if (p.has_tiles) hipLaunchKernelGGL(k_proj_linearize<1>, dim3(p.grid_tiles), dim3(256), p.lds_proj_c, st, d, d.cpose, d.clam, d.fcost_c, 2);
+            if (!p.lds_T) HCHK(hipStreamWaitEvent(st, fj[3], 0));
+            hipLaunchKernelGGL((k_step_control<false, false>), dim3(B), dim3(256), 0, st, d);
         }
         PROF(slot, 5, 1);
-    }
-    if (d.init_mode) {                     // Estimator::initFactorGraph: first priors from the solved estimate, then double2vector
-        hipLaunchKernelGGL(k_init_priors, dim3(d.B), dim3(64), 0, st, d, d.init_scratch, d.init_per_window, d.init_kld);
-        if (hc.tail_one_wave) hipLaunchKernelGGL(k_finalize<64>, dim3(d.B), dim3(64), 0, st, d, 0, 0);
-        else hipLaunchKernelGGL(k_finalize<256>, dim3(d.B), dim3(256), 0, st, d, 0, 0);
-        HCHK(hipGetLastError());
-        return ISV_OK;
     }
     // The tail is bound by the window's latency (the GPU is almost idle: a wavefront per window and SIMD in the one-wavefront
     // forms), so k_finalize and MargBackward give a window four wavefronts and run its independent serial chains side by side;
     // the marginalisation record is cleared at the end of k_finalize (ISV_TAIL_ONE_WAVE: the one-wavefront forms and k_marg_clear).
-    if (hc.tail_one_wave) {
-        hipLaunchKernelGGL(k_finalize<64>, dim3(d.B), dim3(64), 0, st, d, hc.no_update ? 0 : 1, 0);
-        hipLaunchKernelGGL(k_marg_clear, dim3(d.B), dim3(64), 0, st, d);
-    } else hipLaunchKernelGGL(k_finalize<256>, dim3(d.B), dim3(256), 0, st, d, hc.no_update ? 0 : 1, 1);
+    if (p.init_mode) hipLaunchKernelGGL(k_init_priors, dim3(B), dim3(64), 0, st, d, d.init_scratch, d.init_per_window, d.init_kld);      // Estimator::initFactorGraph: first priors from the solved estimate, then double2vector
+    if (p.finalize_wide) hipLaunchKernelGGL(k_finalize<256>, dim3(B), dim3(256), 0, st, d, p.do_update, p.clear_marg);
+    else hipLaunchKernelGGL(k_finalize<64>, dim3(B), dim3(64), 0, st, d, p.do_update, 0);
+    if (p.init_mode) {
+        HCHK(hipGetLastError());
+        return ISV_OK;
+    }
+    if (!p.finalize_wide) hipLaunchKernelGGL(k_marg_clear, dim3(B), dim3(64), 0, st, d);
     // MargForward and MargBackward are independent: run them side by side.  The longer one (backward) goes on the main stream
     // so that it is dispatched FIRST: whichever kernel arrives second runs its last workgroups after the first one's when four
     // workgroups of each per CU do not fit together.  They do fit: LDS 4 x 24.4 KB (k_marg_bwd<3>) + 4 x 14.1 KB (k_marg_fwd<64>)
@@ -644,22 +525,18 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     // (k_marg_bwd<3>; per window, in-kernel stamps: build 30.5 -> 25.1, eigen-decomposition 179 -> 104, projections 31 -> 16,
     // KLD 26 -> 18); k_marg_fwd<64> beside it 148 -> 201 us and still ends 13 us before it; k_finalize's start to the later end
     // 357 -> 259 us; step 5.146 -> 5.046 ms.  One window 1.59 -> 1.54 ms, 128 windows 1.88 -> 1.85 ms: the four-wavefront launch
-    // is the default for every batch size.
+    // is the default for every batch size.  (The one-wavefront forms, B = 1 / 64 / 256 / 512: 1.95 / 2.27 / 2.47 / 3.16 ms with the
+    // eigen-decomposition as a launch of its own against 1.98 / 2.35 / 2.55 / 3.25 with the one launch <2>.)
     HCHK(hipEventRecord(fj[0], st)); HCHK(hipStreamWaitEvent(st2, fj[0], 0));
-    // The one-wavefront forms (ISV_TAIL_ONE_WAVE, and what ISV_MARG_ONE_KERNEL / ISV_MARG_SPLIT force): a batch that leaves SIMDs
-    // idle (one wavefront per window: B < 4 n_cus) takes the four-wavefront eigen-decomposition as a launch of its own (B = 1 /
-    // 64 / 256 / 512: 1.95 / 2.27 / 2.47 / 3.16 ms against 1.98 / 2.35 / 2.55 / 3.25), beyond that the one launch <2>
-    const bool marg_one = hc.marg_one_kernel || (!hc.marg_split && hc.cap_batch > 3 * (size_t)hc.n_cus);     // (per handle: the two forms sum their convergence test in different orders)
-    if (!hc.tail_one_wave && !hc.marg_one_kernel && !hc.marg_split) hipLaunchKernelGGL(k_marg_bwd<3>, dim3(d.B), dim3(256), 0, st, d);
-    else if (marg_one) hipLaunchKernelGGL(k_marg_bwd<2>, dim3(d.B), dim3(64), 0, st, d);
+    if (p.marg_bwd == MARG_BWD_FOUR_WAVES) hipLaunchKernelGGL(k_marg_bwd<3>, dim3(B), dim3(256), 0, st, d);
+    else if (p.marg_bwd == MARG_BWD_ONE_LAUNCH) hipLaunchKernelGGL(k_marg_bwd<2>, dim3(B), dim3(64), 0, st, d);
     else {
-        hipLaunchKernelGGL(k_marg_bwd<0>, dim3(d.B), dim3(64), 0, st, d);
-        hipLaunchKernelGGL(k_marg_jacobi<21>, dim3(d.B), dim3(256), 0, st, d);
-        hipLaunchKernelGGL(k_marg_bwd<1>, dim3(d.B), dim3(64), 0, st, d);
+        hipLaunchKernelGGL(k_marg_bwd<0>, dim3(B), dim3(64), 0, st, d);
+        hipLaunchKernelGGL(k_marg_jacobi<21>, dim3(B), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(k_marg_bwd<1>, dim3(B), dim3(64), 0, st, d);
     }
-    // (four wavefronts for the landmark phases while the batch leaves SIMDs idle; same bits either way)
-    if (d.B <= 2 * n_cus) hipLaunchKernelGGL(k_marg_fwd<256>, dim3(d.B), dim3(256), 0, st2, d);
-    else hipLaunchKernelGGL(k_marg_fwd<64>, dim3(d.B), dim3(64), 0, st2, d);
+    if (p.marg_fwd_wide) hipLaunchKernelGGL(k_marg_fwd<256>, dim3(B), dim3(256), 0, st2, d);
+    else hipLaunchKernelGGL(k_marg_fwd<64>, dim3(B), dim3(64), 0, st2, d);
     HCHK(hipEventRecord(fj[1], st2));
     HCHK(hipStreamWaitEvent(st, fj[1], 0));
     HCHK(hipGetLastError());

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * ((NT * (NT + 1) / 2 + TPW - 1) / TPW), MINW) v
 // NT = 5 (the benchmark's 11 frames): 15 wavefronts per workgroup, and two workgroups share a CU only at eight wavefronts
 // per SIMD, i.e. <= 64 VGPRs -- the launch bounds alone let the compiler settle at 66-70 (occupancy 7: ONE workgroup per CU)
 template <> __global__ __launch_bounds__(960) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_rank1_mfma<5, 1, 64, 1, false>(DevBatch d) { rank1_body<5, 1, 64, 1, false>(d); }
-// (every form the solver's per-handle kernel table can name: isv_solver_alloc)
+// (every form the solver's per-handle kernel table can name: isv_solver_kernel)
 template __global__ void k_rank1_mfma<1, 1, 64, 1, false>(DevBatch);
 template __global__ void k_rank1_mfma<1, 1, 64, 1, true>(DevBatch);
 template __global__ void k_rank1_mfma<2, 1, 64, 1, false>(DevBatch);

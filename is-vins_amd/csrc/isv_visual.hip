@@ -20,12 +20,6 @@
 #include "isv_proj_factor.h"
 #include "isv_lin_gram.h"
 
-// lcap: landmarks per window the launch stages (inverse depths + host points: 4 doubles each)
-size_t lin_gram_lds_bytes(int N /* real frames */, bool partials_in_lds, bool ex, int waves, int lcap) {
-    const size_t NP = (size_t)N * (N - 1) / 2;
-    return ((size_t)N * 12 + 12 + (size_t)waves * 16 * lg_xld(ex) + (partials_in_lds ? NP * 84 : 0) + (NP + 2) / 2 + 1 + (NP + 1) / 2 + 1 + 4 * (size_t)lcap) * sizeof(double);
-}
-
 template <bool EX, int LGW>
 __global__ __launch_bounds__(64 * LGW, LGW > 4 ? 2 : (EX ? 2 : 3)) void k_lin_gram(DevBatch d) {
     extern __shared__ __align__(16) double lds[];

@@ -46,13 +46,13 @@ import numpy as np
 import pytest
 
 import step_highprec as sh
+from step_cases import CASES, DEFAULT, MU0, expected_path      # (shared with tests/test_solve_plan.py, which runs the path rules on the CPU)
 from isvins_amd import abi, backend, synth
 
 pytestmark = pytest.mark.gpu
 dp = C.POINTER(C.c_double)
 LD = np.longdouble
 RADIUS = 1e4                 # initial_trust_region_radius (k_init_state)
-MU0 = 1e-8                   # DoglegStrategy's min_mu, the first slot's mu (k_init_state)
 
 MARGIN = 16.0                # vectors: 4 x 3.10 = 12.4 -> 16
 MARGIN_MODEL = 256.0         # model: 4 x 62.76 = 251 -> 256 (no ratio reaches the 100 that would make it a finding)
@@ -101,53 +101,6 @@ def make_state(oracle, spec):
     return ws
 
 
-# ---- the cases ------------------------------------------------------------------------------------------------------------
-# state: "x0" as synthesised | a number = the perturbation of test_linearize_at_perturbed_priors times it | "converged".
-# The magnitudes were chosen on the CPU (the reference on the oracle's strips) so that all three dogleg branches occur at radius 1e4.
-def _c(N, Nvo, L, wid, state="x0", **kw):
-    return dict(N=N, Nvo=Nvo, L=L, wid=wid, state=state, **kw)
-
-
-DEFAULT = dict(fused_visual=1, fused_control=1, solve_st=0, split=0, lds_T=1)
-CASES = {
-    # window shapes on the default small-batch handle: chain split everywhere on the LDS path; k_lin_gram_chain + k_pose_dogleg up to
-    # N = 11, the long-window k_lin_gram_chain beyond, with the rank-1 downdates inside it (KR_LIN_GRAM_CHAIN_R1) where the panel has
-    # seven tiles: N = 16 .. 18, here n18_l120 (at N = 12 the panel has five: no R1 form is instantiated for it)
-    "n3_l25": _c(3, 2, 25, 95),
-    "n4_l40": _c(4, 2, 40, 30, 1.0),
-    "n11_l63": _c(11, 5, 63, 31),
-    "n11_l64": _c(11, 5, 64, 32, 1.0),
-    "n11_l65": _c(11, 5, 65, 31, 1.0),
-    "n11_l150": _c(11, 5, 150, 3, "converged"),
-    "n12_l100": _c(12, 5, 100, 50, 3.0),
-    "n18_l120": _c(18, 8, 120, 50, 1.0),
-    "n20_l100": _c(20, 8, 100, 51, "converged"),
-    "n21_l60_dense": _c(21, 10, 60, 52, expect=dict(lds_T=0)),
-    # track structure
-    "tracks_two_frames": _c(11, 5, 100, 60, make=dict(max_track=2)),
-    "tracks_whole_window": _c(11, 5, 100, 61, 1.0, make=dict(host_frames=(0, 1))),
-    "frames_without_landmarks": _c(11, 5, 100, 62, make=dict(host_frames=(0, 3))),
-    # free extrinsic (N = 19: the largest it allows)
-    "ex_n11_l100": _c(11, 5, 100, 0, ex=1),
-    "ex_n19_l80": _c(19, 8, 80, 50, 1.0, ex=1),
-    # the split landmark elimination (four 64-landmark passes) and k_backsub_split (lg_lcap > 1024)
-    "split_l193": _c(11, 5, 193, 22, expect=dict(split=1)),
-    "backsub_split_l1025": _c(11, 5, 1025, 23, expect=dict(split=1)),
-    # a ragged batch in a handle whose capacity selects k_build_solve_st: the w * n and lm_off offsets
-    "ragged_batch_st": _c(11, 5, 120, 10, 1.0, Ls=[37, 120, 64], max_batch=640, expect=dict(solve_st=1, fused_control=None)),
-    # the mu x 10 retry: one forced failure, mu = 1e-8 * 10 (k_build_solve_sb: "mu *= 10.0; attempt++")
-    "mu_retry": _c(11, 5, 100, 7, env=dict(ISV_DEBUG_FORCE_RETRY="1"), mu=MU0 * 10.0),
-}
-# kernel-table variants (environment read at handle creation).  With ISV_DEBUG_PATH the library names the handle's choices and every
-# enqueue's on stderr; expected_path() below restates what isv_solver_alloc / isv_solver_enqueue decide and run_case asserts all of it.
-VARIANTS = {"ISV_CHAIN_SPLIT": ("0", {}), "ISV_SOLVE_ST": ("1", dict(solve_st=1)), "ISV_NO_POSE_DOGLEG": ("1", {}),
-            "ISV_LEGACY_VISUAL": ("1", dict(fused_visual=0)), "ISV_SPLIT_CONTROL": ("1", dict(fused_control=0)),
-            "ISV_GENERIC_N": ("1", {}), "ISV_LG_BATCH_WAVES": ("1", {})}
-for _name, (_val, _exp) in VARIANTS.items():
-    CASES[f"{_name.lower()[4:]}_n11"] = _c(11, 5, 100, 7, 1.0, env={_name: _val}, expect=_exp)
-    CASES[f"{_name.lower()[4:]}_n18"] = _c(18, 8, 120, 50, env={_name: _val}, expect=_exp)
-
-
 @contextlib.contextmanager
 def environment(env):
     old = {k: os.environ.get(k) for k in env}
@@ -160,30 +113,6 @@ def environment(env):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-
-
-def expected_path(spec, lds_T, B, Lmax):
-    """what the handle and the enqueue must report (csrc/isv_solver.hip), from the case alone"""
-    env = spec.get("env", {})
-    on = lambda k: int(k in env and env[k] != "0")
-    Nd = spec["N"] + spec.get("ex", 0)                          # device frames
-    solve_st = int(bool(lds_T) and (on("ISV_SOLVE_ST") or spec.get("max_batch", 1) > 512))
-    chain_split = int(bool(lds_T) and not solve_st and env.get("ISV_CHAIN_SPLIT") != "0")
-    gn, legacy = on("ISV_GENERIC_N"), on("ISV_LEGACY_VISUAL")
-    pd_kernel = int(chain_split and Nd <= 11 and not on("ISV_NO_POSE_DOGLEG"))
-    nt = (6 * Nd + 16) // 16                                     # 16-column tiles of the rank-1 panel
-    r1_kernel = int(chain_split and not spec.get("ex") and not gn and Nd > 11 and nt == 7)
-    fused = int(bool(lds_T) and not legacy)
-    lgw = 8 if fused and not on("ISV_LG_BATCH_WAVES") else 4
-    lg_chain = int(chain_split and fused and lgw == 8)
-    lcap = 32 * ((Lmax + 31) // 32)
-    split = int(bool(lds_T) and not spec.get("ex") and (lcap + 63) // 64 >= 4 and spec.get("max_batch", 1) == 1)
-    bsub = int(split and lcap > 1024)
-    fuse_control = int(bool(lds_T) and not on("ISV_SPLIT_CONTROL"))
-    return dict(chain_split=chain_split, generic_n=gn, no_pose_dogleg=on("ISV_NO_POSE_DOGLEG"), lg_batch_waves=on("ISV_LG_BATCH_WAVES"),
-                split_control=on("ISV_SPLIT_CONTROL"), legacy_visual=legacy, pose_dogleg_kernel=pd_kernel, r1_in_lg_kernel=r1_kernel,
-                B=B, lg_lcap=lcap, fused=fused, lgw=lgw, lg_chain=lg_chain, r1_in_lg=int(lg_chain and r1_kernel and not split),
-                split=split, bsub_split=bsub, fuse_control=fuse_control, pose_dogleg=int(pd_kernel and fuse_control and not bsub))
 
 
 # ---- one case -------------------------------------------------------------------------------------------------------------
