@@ -23,6 +23,7 @@
 #include "isv_kernels.h"
 #include "isv_device_math.h"
 #include "isv_chain.h"
+#include "isv_dogleg.h"            // backsub_landmark
 
 // threads per window: 256 (4 wavefronts; four workgroups per CU) for N <= 11, 512 (8 wavefronts; two per CU) for long windows
 #define ST_THREADS(BIG) ((BIG) ? 512 : 256)
@@ -140,6 +141,11 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
     const double *V = d.Tvis + (size_t)w * d.tvis_sz;
     const double *H = d.imu_H + (size_t)w * (N - 1) * ISV_IMU_H;
     const double *PH = d.prior_H + (size_t)w * d.prior_H_sz;
+    // d.bsub_in_solve (short windows): this kernel also back-substitutes the window's landmarks, before its outputs (below).  z_p and u_p
+    // (pose parts) share ONE stride-15 array over the dead pose blocks, behind the chain recurrences' 45 N doubles: z_p at 15 f + 0 .. 5,
+    // u_p at 15 f + 6 .. 11 (60 N <= 18 N (N + 1) from three frames on: isv_solve_plan.h)
+    const bool bsub = !BIG && d.bsub_in_solve;
+    double *const zu = Spp + 45 * N;
     double *ws = d.st_ws + (size_t)w * st_ws_doubles(N);
     double *gDinv = ws, *gC = ws + 81 * N, *gY = ws + 162 * N, *gYi = gY + st_ws_y(N);
 
@@ -932,6 +938,13 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             continue;
         }
         // ---- backward substitution (the forward one rode along with the factorisations) ------------------------------------
+        // d.bsub_in_solve: the landmark back-substitution (before the outputs) needs the pose part of z_p = sc y and of u_p in LDS.  Wavefronts
+        // 2 and 3, idle until the pose part of y is final, request their entry of u_p NOW (d.up as the scaling phase stored it: barriers
+        // lie between), one pose entry per lane, and stage both behind the barrier that makes the pose part of y final
+        const int bs_e = t - 128, bs_i = 15 * (bs_e / 6) + bs_e % 6;       // (wavefronts 2, 3: pose entry bs_e < 6 N <= 66 of z_p / u_p)
+        const bool bs_stage = bsub && bs_e >= 0 && bs_e < n6;
+        double bs_u = 0.0;
+        if (bs_stage) bs_u = d.up[(size_t)w * n + bs_i];
         // pose block: one wavefront, right-hand side in REGISTERS (k_build_solve_sb's routine)
         if (wv == 0) {
             ISV_PHASE_IDS();
@@ -966,6 +979,10 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             if (hasPB) y[15 * fB + c6] = yp1;
         }
         __syncthreads();
+        if (bs_stage) { zu[bs_i] = sc[bs_i] * y[bs_i]; zu[bs_i + 6] = bs_u; }     // (the product the outputs store to d.zp; visible behind the next barrier)
+#ifdef ISV_STAMP
+        const unsigned long long bs_t0 = wall_clock64();     // slot 44: wavefront 2 from here to the barrier before the outputs (it only meets barriers)
+#endif
 #if ST_NO_YSPILL
         // chain rhs -= v_i, v_i = Y_i'^T x_pose, WITHOUT the nodes' Y' (round 5: they are not spilled): Y_p = E_p - Y_j' C_j'^T (E_p: the
         // node's own three pose x speed/bias blocks, j: its child; two children for the middle node), so
@@ -1046,6 +1063,9 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
             __syncthreads();
             if (wv == 0) { for (int i = M - 1; i >= 0; i--) node_bwd(i, i + 1); }
             else if (wv == 1) { for (int i = M + 1; i <= N - 1; i++) node_bwd(i, i - 1); }
+#ifdef ISV_STAMP
+            if (t_outer == 128) d.dbg[(size_t)w * 64 + 44] += (double)(wall_clock64() - bs_t0);
+#endif
         }
 #else
         // chain rhs -= Y_i'^T x_pose from the global scratch (column-major per node: a thread reads contiguous rows);
@@ -1110,6 +1130,16 @@ __global__ __launch_bounds__(ST_THREADS(BIG), 4) void k_build_solve_st(DevBatch 
         break;
     }
     const int t = t_outer, lane = t & 63;
+    if (bsub && !ls_fail) {
+        // the landmark back-substitution k_dogleg otherwise opens with (backsub_landmark, isv_dogleg.h: the same routine on the same
+        // inputs, so d.gn_l and d.lm_aterm get the same bits), with the kernel's final mu.  Here the workgroups of a launch are out of step
+        // by tens of microseconds, so their reads of the w vectors are spread out; at the top of k_dogleg all windows read them at once
+        // (measured, 1024 windows of 11 frames / 300 landmarks: 8 us here against 17 us there; run beside the chain recurrences on
+        // wavefronts 2 and 3 instead, a 128-landmark trip takes 5-6 us of a 5 us window and holds the barriers up:
+        // profiles/backsub_in_solve.txt).  (A window that stops at the gradient tolerance below has them written too; nobody reads them.)
+        const int fw0 = d.f_off[w];
+        for (int l = l0 + t; l < l1; l += LT) backsub_landmark<false>(d, l, fw0, zu, zu + 6, mu);
+    }
     if (!ls_fail) {
         for (int e = t; e < n; e += LT) {
             d.zp[(size_t)w * n + e] = sc[e] * y[e];

@@ -39,7 +39,8 @@ DEV void block_sums(double (&v)[K], double *red /* >= 4 K doubles */, int t) {
 #define DSTAMP(k) do {} while (0)
 #endif
 // back-substitution of ONE eliminated landmark (schur_eliminator BackSubstitute) + its term of the Cauchy-point denominator,
-// from the packed w vectors; zs / us: the window's z_p / u_p in LDS.  Shared by k_dogleg and the multi-workgroup k_backsub_split.
+// from the packed w vectors; zs / us: the window's z_p / u_p in LDS (stride 15; the pose entries are read).  Shared by k_dogleg, the multi-workgroup k_backsub_split
+// and k_build_solve_st (d.bsub_in_solve).
 template <bool EX>
 DEV void backsub_landmark(const DevBatch &d, const int l, const int fw0, const double *zs, const double *us, const double mu) {
             // (round 3: ONE metadata word instead of three dependent index loads; the landmark scalars are requested
@@ -112,7 +113,7 @@ DEV void dogleg_body(DevBatch &d, const int w, const int t, double *red) {
     }
     double a = 0, b = 0, c = 0, e = 0;
     for (int i = t; i < n; i += 256) { a += gp[i] * gp[i]; b += gnp[i] * gnp[i]; c += gp[i] * gnp[i]; }
-    if (st.fresh && !d.bs_split) {          // (bs_split: k_backsub_split has done this on many CUs)
+    if (st.fresh && !d.bs_split && !d.bsub_in_solve) {      // (bs_split: k_backsub_split has done this on many CUs; bsub_in_solve: k_build_solve_st, before its outputs)
         // back-substitution of the eliminated landmarks (schur_eliminator BackSubstitute) + the landmark
         // terms of the Cauchy-point denominator, from the w vectors (one landmark per thread and pass)
         extern __shared__ __align__(16) double dyn0[];

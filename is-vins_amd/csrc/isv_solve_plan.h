@@ -80,6 +80,7 @@ struct SolveEnv {
     bool tail_one_wave = false;       // ISV_TAIL_ONE_WAVE (A/B and test hook): the one-wavefront tail -- k_finalize<64> + k_marg_clear, and MargBackward as
                                       // k_marg_bwd<2> (max_batch > 3 n_cus) or build / k_marg_jacobi / project -- in place of k_finalize<256> and k_marg_bwd<3> (same bits)
     bool r1_dense = false;            // ISV_R1_DENSE (A/B and test hook): k_rank1_mfma's dense MFMA loop, every landmark through every tile (same bits)
+    bool bsub_in_dogleg = false;      // ISV_BSUB_IN_DOGLEG (A/B and test hook): the landmark back-substitution stays in k_dogleg, never inside k_build_solve_st (same bits)
     bool no_update = false;           // ISV_DEBUG_NO_UPDATE (sensitivity study, tests/test_sequence_long.py; the oracle has the same hook): skip the update() of
                                       // the prior factors' pseudo-measurements after the solve (src/estimator.cpp:1133-1144).  NOT the reference's behaviour.
     bool debug_path = false;          // ISV_DEBUG_PATH: stderr lines naming the handle's and every enqueue's kernel choices (tests assert them)
@@ -236,6 +237,7 @@ struct UploadPlan {
     bool dg_stage_ph = false;                 // k_dogleg stages the priors' J^T J record in LDS: while that keeps the batch in one resident round
     bool sw_global = false;                   // the pair partials in the global scratch (more than one workgroup per CU: trade LDS for occupancy)
     bool bsub_split = false;                  // DevBatch::bs_split: k_backsub_split does the landmark back-substitution (long windows only)
+    bool bsub_in_solve = false;               // DevBatch::bsub_in_solve: k_build_solve_st does it before its outputs (short windows); k_dogleg skips it
     bool lds_T = false, chain_split = false, solve_st = false, init_mode = false;
     bool control_in_wg = false;               // the candidate evaluation in the per-window control kernel (not for windows so long that it would serialise)
     bool fuse_control = false;                // dogleg + step control in one kernel: while the batch fits ONE resident round of it
@@ -305,6 +307,10 @@ inline UploadPlan plan_upload(const HandlePlan &h, const SolveDevice &dev, const
     p.r1_in_lg = p.lg_chain && K[KR_LIN_GRAM_CHAIN_R1].inst != KI_NONE && !p.split;
     // k_backsub_split pays for LONG windows only: ~2.5 us for 300 landmarks inside k_dogleg against 6-8 us for the extra launch
     p.bsub_split = p.split && p.lg_lcap > 1024;
+    // ... and a short window of a k_build_solve_st handle has it done by that kernel, before its outputs: its workgroups are out of step
+    // by then, k_dogleg's all read their w vectors at once (fused uploads, constant extrinsic: backsub_landmark<false>).  Three frames at
+    // least: z_p and u_p are staged over the dead pose blocks behind the chain recurrences' 45 N doubles, 60 N <= 18 N (N + 1)
+    p.bsub_in_solve = h.solve_st && p.fused && s.N >= 3 && s.N <= 11 && !ex && !p.bsub_split && !e.bsub_in_dogleg;
     const size_t lds_pd = plan_max(K[KR_POSE].lds, lds_dgc);
     p.pose_dogleg = K[KR_POSE_DOGLEG].inst != KI_NONE && p.fuse_control && !p.bsub_split && lds_pd + ISV_WG_STATIC_LDS <= ISV_LDS_PER_CU;
 

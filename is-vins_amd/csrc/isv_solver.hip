@@ -280,7 +280,7 @@ static SolveEnv solve_env_read() {
     e.lg_batch_waves = on("ISV_LG_BATCH_WAVES"); e.debug_sw_global = on("ISV_DEBUG_SW_GLOBAL"); e.legacy_visual = on("ISV_LEGACY_VISUAL");
     e.no_split = on("ISV_NO_SPLIT"); e.no_update = on("ISV_DEBUG_NO_UPDATE"); e.no_pose_dogleg = on("ISV_NO_POSE_DOGLEG");
     e.marg_one_kernel = on("ISV_MARG_ONE_KERNEL"); e.marg_split = on("ISV_MARG_SPLIT"); e.tail_one_wave = on("ISV_TAIL_ONE_WAVE");
-    e.r1_dense = on("ISV_R1_DENSE"); e.debug_path = on("ISV_DEBUG_PATH");
+    e.r1_dense = on("ISV_R1_DENSE"); e.bsub_in_dogleg = on("ISV_BSUB_IN_DOGLEG"); e.debug_path = on("ISV_DEBUG_PATH");
     e.solve_st = tri("ISV_SOLVE_ST"); e.chain_split = tri("ISV_CHAIN_SPLIT");
     return e;
 }
@@ -410,6 +410,7 @@ int isv_solver_enqueue(DevBatch &d, const SolverHost &hc, hipStream_t st, hipStr
     const RolePlan *K = hc.plan.roles;
     const unsigned B = (unsigned)p.B;
     d.ctl_stage_lm = p.ctl_stage_lm ? 1 : 0; d.dg_stage_ph = p.dg_stage_ph ? 1 : 0; d.sw_global = p.sw_global ? 1 : 0; d.bs_split = p.bsub_split ? 1 : 0;
+    d.bsub_in_solve = p.bsub_in_solve ? 1 : 0;
     if (hc.env.debug_path) { char line[512]; plan_format_enqueue(line, sizeof(line), p); fputs(line, stderr); }
     if (hc.env.one_stream) st2 = st;            // diagnostics: serialise everything on one stream (per-kernel timelines)
     hipLaunchKernelGGL(k_init_state, dim3(p.grid_init_state), dim3(64), 0, st, d);
