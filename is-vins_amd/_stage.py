@@ -1,4 +1,4 @@
-"""What the mirrors of the batched stages on their own handles share (loop.py, bow.py, keyframe.py, tracker.py, detect.py, equalize.py, reject.py, frontend.py, exrot.py): binding
+"""What the mirrors of the batched stages on their own handles share (loop.py, bow.py, keyframe.py, tracker.py, detect.py, equalize.py, reject.py, frontend.py, exrot.py, preint.py): binding
 a library's entry points once, the handle object's life and error texts, and the pre-filled output arrays."""
 import ctypes as C
 

@@ -1,7 +1,7 @@
 // isv_stage_launch.h -- the host side every batched stage shares: the three initialisation stages on a backend handle
 // (isv_initial.hip, isv_sfm.hip, isv_relpose.hip), the loop-closure verification (isv_loop.hip), the loop detection
 // (isv_bow.hip), the keyframe extraction (isv_keyframe.hip) and the feature tracking (isv_tracker.hip), each of the four on its
-// own handle (StageHandle), as is the camera-IMU rotation calibration (isv_exrot.hip), and the feature detection (isv_detect.hip), the CLAHE (isv_equalize.hip) and the outlier rejection
+// own handle (StageHandle), as are the camera-IMU rotation calibration (isv_exrot.hip) and the IMU pre-integration (isv_preint.hip), and the feature detection (isv_detect.hip), the CLAHE (isv_equalize.hip) and the outlier rejection
 // (isv_reject.hip) on a tracker handle's device and stream.
 // A stage call packs its problems into one pageable upload block, launches its kernels on the context's stream and copies its
 // outputs back, synchronously; the launcher owns the events around and between the kernels and the times read from them.  A stage
